@@ -12,8 +12,11 @@ N > 1 (torchrun, one rank per GPU): the SAME video is sharded along the frame ax
 windows); every rank runs towers + stream on its shard, keeps its K/V shard resident and the per-layer
 cross-attention partials are all-gathered (RCCL) and LSE-merged — strong scaling of one query.
 
-Prints ONE JSON line (rank 0).  Extra objects: roofline (dominant kernel family = MFMA GEMM, timed with
-HIP events on the launch stream), cpu_baseline (the CPU oracle timed on a bounded slice of this workload).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`, stage times, the first-token logit digest); `--dump-outputs DIR` also saves what the last timed step computed.
+`--full` adds the legs that take runs of their own, after the timed steps: roofline (dominant kernel family = MFMA GEMM, timed
+with HIP events on the launch stream), decode / s-per-query, verify, the other BASELINE configs and dtype, box_reference,
+preproc and cpu_baseline (the CPU oracle timed on a bounded slice of this workload).
 """
 import argparse
 import json
@@ -75,7 +78,17 @@ def parse():
                     "after the headline workload (default workload, one GPU only)")
     ap.add_argument("--attn-gain", type=float, default=ATTN_GAIN, help="factor on the decoder's random q_proj weights (a power of two is exact in "
                                                                         "bf16/fp16): sharper text->video attention; 1 = SURVEY 8d's plain randn * 0.02")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every leg beside the headline: the instrumented pass "
+                    "(kernel_families, roofline), the decode leg (s/query), verify, the other BASELINE configs and dtype, box_reference, preproc and "
+                    "cpu_baseline (each --no-* option above switches its leg off again).  Without it a run times the K prefill steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32; "
+                                                                          "first-token logits and tokens in full, fixed samples of the token embeddings and K/V caches)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:              # a plain run is the headline alone
+        a.no_kernel_timer = a.no_verify = a.no_other_configs = a.no_other_dtype = a.no_preproc = a.no_cpu_baseline = True
+    return a
 
 
 def self_launch(a):
@@ -324,6 +337,39 @@ def _cache_rows(mm, li, rows, nkv, hd):
     pos = (tk & ~15) | (8 * ((x >> 2) & 1) + (x & 3) + 4 * (x >> 3))                # perm16 key order inside a 32-key sub-tile
     v = mm.vtc[li][:, r >> 5, :, pos]                                               # [n, nkv, hd]
     return k.float().cpu(), v.reshape(len(rows), nkv * hd).float().cpu()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, logits, tokens, fi, fa, mm, nkv, hd):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, as float32 .npy files, so that two builds can be compared output
+    for output on the same seeded inputs.  In full: the first-token logits [queries, vocab] and their argmax.  Sampled (fixed seed, so the
+    same rows every run): 256 rows of the video token embeddings, 128 of the audio token embeddings, and the K / V cache rows of 256 video
+    and 128 audio keys at the first and the last decoder layer.  Under N ranks these are rank 0's local rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rs = np.random.RandomState(0)
+
+    def pick(n, k):
+        return np.sort(rs.choice(n, min(n, k), replace=False)) if n > 0 else np.zeros(0, dtype=np.int64)
+
+    def rows(x, k):
+        if x is None or x.shape[0] == 0:
+            return np.zeros((0, 0), dtype=np.float32)
+        return x[torch.as_tensor(pick(x.shape[0], k), device=x.device)].float().cpu().numpy()
+
+    keys = np.concatenate([mm.img_start + pick(mm.n_img, 256), mm.aud_start + pick(mm.n_aud, 128)]).tolist()
+    kv = [_cache_rows(mm, li, keys, nkv, hd) for li in (0, mm.kc.shape[0] - 1)] if keys else []
+    out = {"first_token_logits": logits.float().cpu().numpy(), "first_token": tokens.cpu().numpy().astype(np.float32),
+           "video_tokens_sample": rows(fi, 256), "audio_tokens_sample": rows(fa, 128),
+           "k_cache_sample": np.stack([k.numpy() for k, _ in kv]) if kv else np.zeros((0, 0, 0), dtype=np.float32),
+           "v_cache_sample": np.stack([v.numpy() for _, v in kv]) if kv else np.zeros((0, 0, 0), dtype=np.float32)}
+    total = sum(x.nbytes for x in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"bench: --dump-outputs would write {total / 2**20:.1f} MB, more than {DUMP_LIMIT_BYTES >> 20} MB")
+    for name, x in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), x)
 
 
 def verify_against_oracle(a, cfg, eng, model, make_weights, dtype, dev, world, rank, pixel, mel, f0, f1, T, c0, c1, audio_size, Nv, Na,
@@ -608,7 +654,8 @@ def main():
 
     for _ in range(a.warmup):
         wmm, wts, wnxt = step()
-        decode_eager(wts, wmm, wnxt, min(2, a.decode_steps))   # warm the decode kernels too (code objects, workspaces)
+        if a.full:
+            decode_eager(wts, wmm, wnxt, min(2, a.decode_steps))   # warm the decode leg's kernels too (code objects, workspaces)
         del wmm, wts, wnxt
     # ---- timed region: K steps with NO per-launch instrumentation (the headline number) ----
     checks.clear()
@@ -640,6 +687,8 @@ def main():
     logit_checksum = float(lg0.float().abs().sum())
     logits_sha256 = hashlib.sha256(lg0.contiguous().view(torch.int16).cpu().numpy().tobytes()).hexdigest()
     n_bitwise = len(checks)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, checks[-1][0], checks[-1][1], last_feats[0], last_feats[1], mm, cfg.num_key_value_heads, cfg.head_dim)
     checks.clear()
 
     # ---- second pass (untimed in `value`): every C-ABI launch bracketed with HIP events on the launch stream -> kernel families ----
@@ -663,24 +712,25 @@ def main():
     # ---- decode leg (s/query = prefill + n_new decode steps on the resident caches) ----
     # --decode-graph: the step is captured once in a hipGraph (vidi_amd/engine.py:make_decode_graph) and replayed;
     # the capture (one eager step + graph build) is timed inside the leg, so s/query pays for it.
-    torch.cuda.synchronize()
     # over shards the captured step includes the per-layer RCCL all-gathers (engine.make_decode_graph); the gloo test transport cannot be captured
     use_graph = a.decode_graph and a.decode_steps >= 2 and (world == 1 or dist.get_backend() == "nccl")
     t_capture = 0.0
-    td0 = time.perf_counter()
-    if use_graph:
-        nxt, replay = eng.make_decode_graph(ts, mm, nxt)
-        int(nxt[0])
-        t_capture = time.perf_counter() - td0
-        for _ in range(a.decode_steps - 1):
-            nxt = replay(nxt)
-            int(nxt[0])                                       # per-token D2H sync, as a stopping criterion needs
-    else:
-        nxt = decode_eager(ts, mm, nxt, a.decode_steps)
-    torch.cuda.synchronize()
-    t_total_decode = time.perf_counter() - td0
-    t_decode = t_total_decode / max(1, a.decode_steps)
-    t_replay = (t_total_decode - t_capture) / max(1, a.decode_steps - 1) if use_graph else t_decode
+    if a.full:
+        torch.cuda.synchronize()
+        td0 = time.perf_counter()
+        if use_graph:
+            nxt, replay = eng.make_decode_graph(ts, mm, nxt)
+            int(nxt[0])
+            t_capture = time.perf_counter() - td0
+            for _ in range(a.decode_steps - 1):
+                nxt = replay(nxt)
+                int(nxt[0])                                       # per-token D2H sync, as a stopping criterion needs
+        else:
+            nxt = decode_eager(ts, mm, nxt, a.decode_steps)
+        torch.cuda.synchronize()
+        t_total_decode = time.perf_counter() - td0
+        t_decode = t_total_decode / max(1, a.decode_steps)
+        t_replay = (t_total_decode - t_capture) / max(1, a.decode_steps - 1) if use_graph else t_decode
 
     # ---- verification leg (untimed): sampled frames' token embeddings and sampled K/V-cache rows against the CPU oracle ----
     verify = None
@@ -782,10 +832,11 @@ def main():
 
     # ---- box-speed reference (untimed): frozen probe kernels, so that records from different boxes can be normalised ----
     box = None
-    try:
-        box = hip.probe_box(pixel)
-    except Exception as e:
-        box = {"error": repr(e)}
+    if a.full:
+        try:
+            box = hip.probe_box(pixel)
+        except Exception as e:
+            box = {"error": repr(e)}
 
     fam = timer.summary() if timer is not None else {}
     roof = None
@@ -828,18 +879,20 @@ def main():
                    "frames": T, "fps": a.fps, "video_tokens": Nv, "audio_tokens": Na, "prompt_tokens": plens[0] if len(set(plens)) == 1 else plens,
                    "parallelism": ("single GPU" if world == 1 else f"frame-shard x{world} (towers sharded, RCCL all-gather of visual / audio tokens, decoder replicated)"
                                    if gather_mode else f"frame-shard x{world} (K/V shards resident, LSE-merged cross-attention)")},
-        "dist_mode": a.dist_mode if world > 1 else None,
-        # one video, `queries` prompts answered together: the encode + stream prefill is shared
-        "sec_per_query": (ms_per_step / 1e3 + a.decode_steps * t_decode) / a.queries, "decode_ms_per_token": t_decode * 1e3,
-        "sec_per_query_cached": (stage_ms.get("text_prefill", 0.0) / a.steps / 1e3 + a.decode_steps * t_decode) / a.queries,
-        "queries": a.queries, "decode_tokens": a.decode_steps, "decode_graph": bool(use_graph), "decode_graph_capture_ms": t_capture * 1e3,
-        "decode_replay_ms_per_token": t_replay * 1e3, "frames_per_s": T * a.steps / dt,
+        "dist_mode": a.dist_mode if world > 1 else None, "queries": a.queries, "frames_per_s": T * a.steps / dt,
         "stage_ms_per_step": {k: v / a.steps for k, v in stage_ms.items()},
         "first_token": first_token, "first_token_logit_abs_sum": logit_checksum,
-        "first_token_logits_sha256": logits_sha256, "steps_with_bitwise_identical_first_token_logits": n_bitwise, "attn_gain": a.attn_gain, "verify": verify,
-        "kernel_families": fams, "kernel_family_steps": timer_steps,
-        "roofline": roof, "box_reference": box, "other_baseline_configs": other,
+        "first_token_logits_sha256": logits_sha256, "steps_with_bitwise_identical_first_token_logits": n_bitwise, "attn_gain": a.attn_gain,
     }
+    if a.full:
+        res.update({
+            # one video, `queries` prompts answered together: the encode + stream prefill is shared
+            "sec_per_query": (ms_per_step / 1e3 + a.decode_steps * t_decode) / a.queries, "decode_ms_per_token": t_decode * 1e3,
+            "sec_per_query_cached": (stage_ms.get("text_prefill", 0.0) / a.steps / 1e3 + a.decode_steps * t_decode) / a.queries,
+            "decode_tokens": a.decode_steps, "decode_graph": bool(use_graph), "decode_graph_capture_ms": t_capture * 1e3,
+            "decode_replay_ms_per_token": t_replay * 1e3, "verify": verify, "kernel_families": fams, "kernel_family_steps": timer_steps,
+            "roofline": roof, "box_reference": box, "other_baseline_configs": other,
+        })
     if world == 1 and not a.no_preproc:
         # SURVEY §8f-2 leg, reported beside the metric and never part of `value`: decoded RGB frames (uint8) and 16 kHz PCM
         # resident in HBM -> pixel_values / input_features through csrc/preproc.hip (bit-exact with PIL + the HF processors)

@@ -61,6 +61,8 @@ def main():
     gp, pp = os.path.join(HERE, "vue_synth_gt.json"), os.path.join(HERE, "vue_synth_pred.json")
     json.dump(gt, open(gp, "w")); json.dump(pred, open(pp, "w"))
     out["synthetic"] = scores(Q, gp, pp)
+    # the same set under VUE_TR's (v1) scorer, which lacks v2's "empty ground truth and empty answer -> precision 1" rule (query 3)
+    out["synthetic_v1"] = scores(sys.modules["ref_qa_eval_v1"], gp, pp)
     json.dump(out, open(os.path.join(HERE, "reference_vue.json"), "w"), indent=1)
     print("wrote reference_vue.json:", list(out))
 

@@ -33,8 +33,17 @@ def test_synthetic_matches_reference_execution():
     assert 0.0 < got["overall"]["iou"] < 1.0
 
 
+def test_synthetic_matches_reference_execution_v1():
+    """the VUE_TR (v1) scorer on the same set: no "empty ground truth and empty answer -> precision 1" rule (query 3)"""
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        got = E.score_predictions(os.path.join(GOLD, "vue_synth_pred.json"), os.path.join(GOLD, "vue_synth_gt.json"), version=1)
+    check(got, REF["synthetic_v1"])
+    assert REF["synthetic_v1"]["overall"]["precision"] != REF["synthetic"]["overall"]["precision"]
+
+
 @pytest.mark.skipif(not os.path.isdir("/root/reference/VUE_TR_V2"), reason="reference tree (ground truth + shipped results) not present")
-@pytest.mark.parametrize("key", [k for k in REF if k != "synthetic"])
+@pytest.mark.parametrize("key", [k for k in REF if not k.startswith("synthetic")])
 def test_shipped_results_match_reference_execution(key):
     tag, fname = key.split(":")
     d, gt = ("/root/reference/VUE_TR_V2", "VUE-TRv2_ground_truth.json") if tag == "v2" else ("/root/reference/VUE_TR", "VUE-TR_ground_truth.json")

@@ -41,14 +41,14 @@ probe)
 dist8g)
   # EIGHT ranks sharing the one GPU (gloo transport): BASELINE's 8-way partition through bench.py end to end in both dist modes; 48 frames (6 per rank; 2 audio windows: six ranks without audio) — every rank of the gather mode holds the FULL K/V, eight of them share 288 GB here
   for m in gather_tokens sharded_stream; do
-    VIDI_DIST_BACKEND=gloo timeout 1500 python bench.py --gpus 8 --dist-mode $m --frames 48 --steps 1 --warmup 1 --no-preproc --no-other-configs --no-kernel-timer --decode-steps 8 > $OUT/bench_dist8_$m.json 2> $OUT/bench_dist8_$m.err; echo "dist8 $m rc=$?"
+    VIDI_DIST_BACKEND=gloo timeout 1500 python bench.py --full --gpus 8 --dist-mode $m --frames 48 --steps 1 --warmup 1 --no-preproc --no-other-configs --no-kernel-timer --decode-steps 8 > $OUT/bench_dist8_$m.json 2> $OUT/bench_dist8_$m.err; echo "dist8 $m rc=$?"
   done
-  timeout 600 python bench.py --frames 48 --steps 1 --warmup 1 --no-preproc --no-cpu-baseline --no-other-configs --no-kernel-timer --decode-steps 8 > $OUT/bench_dist8_ref1.json 2> $OUT/bench_dist8_ref1.err; echo "dist8 ref rc=$?"
+  timeout 600 python bench.py --full --frames 48 --steps 1 --warmup 1 --no-preproc --no-cpu-baseline --no-other-configs --no-kernel-timer --decode-steps 8 > $OUT/bench_dist8_ref1.json 2> $OUT/bench_dist8_ref1.err; echo "dist8 ref rc=$?"
   # the gather mode's bit-identity with one rank holds when every GEMM of a rank's shard takes the SAME kernel as on the whole video: vidi_gemm picks the
   # 128 x 128 tile kernel below 192 tiles of 256 x 256 (another MFMA shape sums in another order) — below 14 frames per rank for the N = 1 152 tower
   # GEMMs, below 3 511 token rows per rank for the projector (18 frames at 196 tokens / frame; BASELINE: 450 frames, 11 250 rows per rank).  World 4 x 24 frames:
-  VIDI_DIST_BACKEND=gloo timeout 1500 python bench.py --gpus 4 --dist-mode gather_tokens --frames 96 --steps 1 --warmup 1 --no-preproc --no-other-configs --no-kernel-timer --decode-steps 4 > $OUT/bench_dist4_gather_tokens_96.json 2> $OUT/bench_dist4_gather_tokens_96.err; echo "dist4 gather 96 rc=$?"
-  timeout 600 python bench.py --frames 96 --steps 1 --warmup 1 --no-preproc --no-cpu-baseline --no-other-configs --no-kernel-timer --decode-steps 4 > $OUT/bench_dist4_ref1_96.json 2> $OUT/bench_dist4_ref1_96.err; echo "dist4 ref 96 rc=$?"
+  VIDI_DIST_BACKEND=gloo timeout 1500 python bench.py --full --gpus 4 --dist-mode gather_tokens --frames 96 --steps 1 --warmup 1 --no-preproc --no-other-configs --no-kernel-timer --decode-steps 4 > $OUT/bench_dist4_gather_tokens_96.json 2> $OUT/bench_dist4_gather_tokens_96.err; echo "dist4 gather 96 rc=$?"
+  timeout 600 python bench.py --full --frames 96 --steps 1 --warmup 1 --no-preproc --no-cpu-baseline --no-other-configs --no-kernel-timer --decode-steps 4 > $OUT/bench_dist4_ref1_96.json 2> $OUT/bench_dist4_ref1_96.err; echo "dist4 ref 96 rc=$?"
   python - <<'PY'
 import json
 for n in ("dist8_gather_tokens", "dist8_sharded_stream", "dist8_ref1", "dist4_gather_tokens_96", "dist4_ref1_96"):
@@ -63,9 +63,9 @@ PY
 dist2g)
   # dist mode gather_tokens (BASELINE configs[3] as worded) next to the sharded stream, two ranks on the one GPU (gloo transport), 10-minute video
   for m in gather_tokens sharded_stream; do
-    VIDI_DIST_BACKEND=gloo timeout 900 python bench.py --gpus 2 --dist-mode $m --frames 600 --steps 1 --warmup 1 --no-preproc --no-other-configs > $OUT/bench_dist2_$m.json 2> $OUT/bench_dist2_$m.err; echo "dist2 $m rc=$?"
+    VIDI_DIST_BACKEND=gloo timeout 900 python bench.py --full --gpus 2 --dist-mode $m --frames 600 --steps 1 --warmup 1 --no-preproc --no-other-configs > $OUT/bench_dist2_$m.json 2> $OUT/bench_dist2_$m.err; echo "dist2 $m rc=$?"
   done
-  timeout 600 python bench.py --frames 600 --steps 1 --warmup 1 --no-preproc --no-cpu-baseline --no-other-configs > $OUT/bench_dist1.json 2> $OUT/bench_dist1.err; echo "dist1 rc=$?"
+  timeout 600 python bench.py --full --frames 600 --steps 1 --warmup 1 --no-preproc --no-cpu-baseline --no-other-configs > $OUT/bench_dist1.json 2> $OUT/bench_dist1.err; echo "dist1 rc=$?"
   python - <<'PY'
 import json
 for n in ("dist2_gather_tokens", "dist2_sharded_stream", "dist1"):
@@ -79,23 +79,23 @@ PY
 smoke)
   timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -6 $OUT/smoke.log ;;
 bench)
-  timeout 1200 python bench.py --steps 3 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; python tools/show_bench.py $OUT/bench.json 2>/dev/null | head -40 ;;
+  timeout 1200 python bench.py --full --steps 3 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; python tools/show_bench.py $OUT/bench.json 2>/dev/null | head -40 ;;
 bench20)
   # the driver's command shape
-  timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench20.json 2> $OUT/bench20.err; echo "bench20 rc=$?"; python tools/show_bench.py $OUT/bench20.json 2>/dev/null | head -40 ;;
+  timeout 1500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench20.json 2> $OUT/bench20.err; echo "bench20 rc=$?"; python tools/show_bench.py $OUT/bench20.json 2>/dev/null | head -40 ;;
 prof)
-  (cd /tmp && timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o r6 -- python $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timer --no-preproc --no-verify --no-other-configs > $OUT/prof_bench.json 2> $OUT/prof.err)
+  (cd /tmp && timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o r6 -- python $REPO/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timer --no-preproc --no-verify --no-other-configs > $OUT/prof_bench.json 2> $OUT/prof.err)
   echo "prof rc=$?"; find $OUT/prof -name '*kernel_stats.csv' | head -3
   # keep the summary, drop the per-dispatch trace (tens of MB)
   find $OUT/prof -name '*kernel_trace.csv' -delete; find $OUT/prof -name '*.db' -delete ;;
 mfma)
-  CMD="python $REPO/bench.py --steps 1 --warmup 0 --decode-steps 2 --no-cpu-baseline --no-kernel-timer --no-preproc --no-verify --no-other-configs"
+  CMD="python $REPO/bench.py --full --steps 1 --warmup 0 --decode-steps 2 --no-cpu-baseline --no-kernel-timer --no-preproc --no-verify --no-other-configs"
   (cd /tmp && timeout 1200 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_mfma -o m -- $CMD > $OUT/pmc_mfma.json 2> $OUT/pmc_mfma.err); echo "mfma rc=$?"
   python tools/mfma_busy_from_pmc.py "$(find $OUT/pmc_mfma -name '*counter_collection.csv' | head -1)" $OUT/mfma_busy.json
   rm -rf $OUT/pmc_mfma ;;
 verify300)
   # the bench's in-run verification leg on the 5-min config (quick)
-  timeout 600 python bench.py --frames 300 --steps 1 --warmup 1 --no-cpu-baseline --no-preproc --no-kernel-timer --decode-steps 4 > $OUT/bench_verify300.json 2> $OUT/bench_verify300.err; echo "verify300 rc=$?"
+  timeout 600 python bench.py --full --frames 300 --steps 1 --warmup 1 --no-cpu-baseline --no-preproc --no-kernel-timer --decode-steps 4 > $OUT/bench_verify300.json 2> $OUT/bench_verify300.err; echo "verify300 rc=$?"
   python tools/show_bench.py $OUT/bench_verify300.json 2>/dev/null | grep -E "value|first_token|verify" || tail -5 $OUT/bench_verify300.err ;;
 epi2)
   bash tools/lab/run_epi2_ab.sh 2>&1 | tail -60 ;;
@@ -103,7 +103,7 @@ abw4n)
   # same-box ABAB of the prefill: 288 x 224 tiles for N = 1 152 (default) against the 256-wide kernel everywhere (VIDI_W4N=0), one library
   : > $OUT/ab_w4n.jsonl
   for r in 1 2; do for sw in 0 1; do
-    VIDI_W4N=$sw timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-preproc --decode-steps 4 2> $OUT/ab_w4n.err | grep '^{' | sed "s/^{/{\"VIDI_W4N\": $sw, /" >> $OUT/ab_w4n.jsonl; echo "abw4n $sw rc=$?"
+    VIDI_W4N=$sw timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-preproc --decode-steps 4 2> $OUT/ab_w4n.err | grep '^{' | sed "s/^{/{\"VIDI_W4N\": $sw, /" >> $OUT/ab_w4n.jsonl; echo "abw4n $sw rc=$?"
   done; done
   python - <<'PY'
 import json
@@ -116,7 +116,7 @@ abqkv)
   # same-box ABAB of the prefill: SigLIP's q | k | v projection on 288 x 224 tiles (default) against the 256-wide kernel (VIDI_W4N_QKV=0), one library
   : > $OUT/ab_qkv.jsonl
   for r in 1 2; do for sw in 0 1; do
-    VIDI_W4N_QKV=$sw timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-preproc --no-other-configs --decode-steps 4 2> $OUT/ab_qkv.err | grep '^{' | sed "s/^{/{\"VIDI_W4N_QKV\": $sw, /" >> $OUT/ab_qkv.jsonl; echo "abqkv $sw rc=$?"
+    VIDI_W4N_QKV=$sw timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-preproc --no-other-configs --decode-steps 4 2> $OUT/ab_qkv.err | grep '^{' | sed "s/^{/{\"VIDI_W4N_QKV\": $sw, /" >> $OUT/ab_qkv.jsonl; echo "abqkv $sw rc=$?"
   done; done
   python - <<'PY'
 import json
@@ -130,7 +130,7 @@ abskinny)
   # the tile GEMM (VIDI_SKINNY_GEMM=0); `stage_ms_per_step.text_prefill` is the number to read
   : > $OUT/ab_skinny.jsonl
   for r in 1 2; do for sw in 0 1; do
-    VIDI_SKINNY_GEMM=$sw timeout 300 python bench.py --frames 300 --steps 5 --warmup 2 --no-cpu-baseline --no-preproc --decode-steps 4 2> $OUT/ab_skinny.err | grep '^{' | sed "s/^{/{\"VIDI_SKINNY_GEMM\": $sw, /" >> $OUT/ab_skinny.jsonl; echo "abskinny $sw rc=$?"
+    VIDI_SKINNY_GEMM=$sw timeout 300 python bench.py --full --frames 300 --steps 5 --warmup 2 --no-cpu-baseline --no-preproc --decode-steps 4 2> $OUT/ab_skinny.err | grep '^{' | sed "s/^{/{\"VIDI_SKINNY_GEMM\": $sw, /" >> $OUT/ab_skinny.jsonl; echo "abskinny $sw rc=$?"
   done; done
   python - <<'PY'
 import json
@@ -143,7 +143,7 @@ abepi)
   # same-box ABAB of the prefill: the product library (epilogue form 2) against tools/build_epi1.sh's build (form 1 everywhere, built in the container)
   : > $OUT/ab_epi.jsonl
   for r in 1 2; do for lib in libvidi_hip_epi1.so libvidi_hip.so; do
-    VIDI_HIP_LIB=$REPO/vidi_amd/$lib timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-preproc --no-verify --decode-steps 4 2> $OUT/ab_epi.err | grep '^{' | sed "s/^{/{\"lib\": \"$lib\", /" >> $OUT/ab_epi.jsonl; echo "abepi $lib rc=$?"
+    VIDI_HIP_LIB=$REPO/vidi_amd/$lib timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-preproc --no-verify --decode-steps 4 2> $OUT/ab_epi.err | grep '^{' | sed "s/^{/{\"lib\": \"$lib\", /" >> $OUT/ab_epi.jsonl; echo "abepi $lib rc=$?"
   done; done
   python - <<'PY'
 import json
@@ -158,8 +158,8 @@ towerbound)
   bash tools/lab/run_tower_bound.sh 2>&1 | tail -90 ;;
 dist8)
   # eight ranks sharing the one GPU (gloo transport): the BASELINE 8-way partition of bench.py end to end on a 10-minute video, and the same video on one rank
-  VIDI_DIST_BACKEND=gloo timeout 1500 python bench.py --gpus 8 --frames 600 --steps 1 --warmup 1 --no-preproc --no-kernel-timer --decode-steps 8 > $OUT/bench_dist8.json 2> $OUT/bench_dist8.err; echo "dist8 rc=$?"
-  timeout 600 python bench.py --frames 600 --steps 1 --warmup 1 --no-preproc --no-cpu-baseline --no-kernel-timer --decode-steps 8 > $OUT/bench_dist8_ref1.json 2> $OUT/bench_dist8_ref1.err; echo "dist8 ref rc=$?"
+  VIDI_DIST_BACKEND=gloo timeout 1500 python bench.py --full --gpus 8 --frames 600 --steps 1 --warmup 1 --no-preproc --no-kernel-timer --decode-steps 8 > $OUT/bench_dist8.json 2> $OUT/bench_dist8.err; echo "dist8 rc=$?"
+  timeout 600 python bench.py --full --frames 600 --steps 1 --warmup 1 --no-preproc --no-cpu-baseline --no-kernel-timer --decode-steps 8 > $OUT/bench_dist8_ref1.json 2> $OUT/bench_dist8_ref1.err; echo "dist8 ref rc=$?"
   python tools/show_bench.py $OUT/bench_dist8.json $OUT/bench_dist8_ref1.json 2>/dev/null | grep -E "value|stages|first_token|verify" ;;
 attn)
   # encoder-attention schedule variants (tools/build_variant.sh ... in the container), same-box A/B
@@ -168,7 +168,7 @@ variants)
   # regression sweep of the other bench configurations on the current build (BASELINE configs[1], [4]-shape, Vidi-7B, fp16, graph decode)
   # "cfg4": BASELINE configs[4] on one GPU — 30 min @2 fps (3 600 frames, 60 audio windows), 8 ragged prompts sharing the video, 128 decoded tokens
   for v in "--frames 300" "--queries 8" "--preset vidi_7b" "--dtype fp16" "--decode-graph" "--fps 2 --queries 8 --ragged-prompts 24 52 --decode-steps 128"; do
-    n=$(echo $v | tr -d ' -' | cut -c1-24); timeout 900 python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-preproc $v > $OUT/bench_$n.json 2> $OUT/bench_$n.err; echo "bench $v rc=$?"
+    n=$(echo $v | tr -d ' -' | cut -c1-24); timeout 900 python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-preproc $v > $OUT/bench_$n.json 2> $OUT/bench_$n.err; echo "bench $v rc=$?"
     python tools/show_bench.py $OUT/bench_$n.json 2>/dev/null | grep -E "value|stages"
   done ;;
 labres)
@@ -200,15 +200,15 @@ dist2)
   # two ranks sharing the one GPU of the box (gloo transport; RCCL refuses two ranks on one device): the torchrun / sharded code path
   # of bench.py end to end, on a 10-minute video so both ranks fit
   # (bench.py launches its own ranks: no torchrun on the command line)
-  VIDI_DIST_BACKEND=gloo timeout 900 python bench.py --gpus 2 --frames 600 --steps 1 --warmup 1 --no-preproc --no-other-configs > $OUT/bench_dist2.json 2> $OUT/bench_dist2.err; echo "dist2 rc=$?"
-  VIDI_DIST_BACKEND=gloo timeout 900 python bench.py --gpus 2 --frames 600 --fps 2 --queries 8 --ragged-prompts 24 52 --decode-steps 64 --steps 1 --warmup 1 --no-preproc \
+  VIDI_DIST_BACKEND=gloo timeout 900 python bench.py --full --gpus 2 --frames 600 --steps 1 --warmup 1 --no-preproc --no-other-configs > $OUT/bench_dist2.json 2> $OUT/bench_dist2.err; echo "dist2 rc=$?"
+  VIDI_DIST_BACKEND=gloo timeout 900 python bench.py --full --gpus 2 --frames 600 --fps 2 --queries 8 --ragged-prompts 24 52 --decode-steps 64 --steps 1 --warmup 1 --no-preproc \
       > $OUT/bench_dist2_q8.json 2> $OUT/bench_dist2_q8.err; echo "dist2 q8 rc=$?"
-  timeout 600 python bench.py --frames 600 --steps 1 --warmup 1 --no-preproc --no-cpu-baseline > $OUT/bench_dist1.json 2> $OUT/bench_dist1.err; echo "dist1 rc=$?"
+  timeout 600 python bench.py --full --frames 600 --steps 1 --warmup 1 --no-preproc --no-cpu-baseline > $OUT/bench_dist1.json 2> $OUT/bench_dist1.err; echo "dist1 rc=$?"
   python tools/show_bench.py $OUT/bench_dist2.json $OUT/bench_dist1.json 2>/dev/null | grep -E "value|stages" ;;
 chunk)
   timeout 900 python tools/bench_vis_chunk.py 3600 > $OUT/vis_chunk.jsonl 2> $OUT/vis_chunk.err; echo "chunk rc=$?"; cat $OUT/vis_chunk.jsonl ;;
 pmc)
-  CMD="python $REPO/bench.py --steps 1 --warmup 0 --decode-steps 2 --no-cpu-baseline --no-kernel-timer --no-preproc --no-verify --no-other-configs"
+  CMD="python $REPO/bench.py --full --steps 1 --warmup 0 --decode-steps 2 --no-cpu-baseline --no-kernel-timer --no-preproc --no-verify --no-other-configs"
   # rocprofv3's counter mode sometimes segfaults within seconds of the first dispatches of this command (round 4: 5 of 7 attempts, either
   # counter, different boxes; the same passes run through when retried): a failed attempt costs ~5 s, so each pass is tried up to 5 times
   for pass in "FETCH_SIZE pmc_fetch f" "WRITE_SIZE pmc_write w"; do
