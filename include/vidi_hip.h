@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define VIDI_ABI_VERSION 5 /* 2: vidi_softcap_argmax takes a caller-owned workspace (the library holds no device state); 3: + vidi_gemm_skinny; 4: (a lab-only revision: LayerNorm statistics in the consumer's K loop, measured 28 % slower, never shipped); 5: + vidi_gemv_mfma (a batch of decode rows on the matrix pipe), vidi_attn_cross_row_tiles_per_block, vidi_probe_* */
+#define VIDI_ABI_VERSION 6 /* 2: vidi_softcap_argmax takes a caller-owned workspace (the library holds no device state); 3: + vidi_gemm_skinny; 4: (a lab-only revision: LayerNorm statistics in the consumer's K loop, measured 28 % slower, never shipped); 5: + vidi_gemv_mfma (a batch of decode rows on the matrix pipe), vidi_attn_cross_row_tiles_per_block, vidi_probe_*; 6: + vidi_attn_cross_seg, vidi_attn_merge_seg (a batch of different videos decoded together) */
 #define VIDI_DT_BF16 0
 #define VIDI_DT_F16 1
 #define VIDI_DT_F32 2 /* output type of the preprocessing kernels only */
@@ -219,6 +219,25 @@ int vidi_attn_merge2_sharded(const float* OpartA, const float* MLA, long long ws
                              const float* OpartB, const float* MLB, long long wsOB, long long wsMLB, void* OutB, float* OutF32B,
                              float* OutMLB, int WB, int zeroB,
                              int nkv, int R, int Rpad, int rpo, int G, int HD, int ldo, int dtype, void* stream);
+
+/* Segmented cross-attention: a batch with ONE VIDEO PER ROW decoded together (flash_attn_varlen_func over the batch's padded video /
+ * audio keys: lmm/dattn/xattn.py:36-103, 123 via gemma.py:81-91; the batch is built by multimodal.py:156-252).  A segment is one video:
+ * query tokens [tok0, tok0 + ntok) of the packed rows of Q and, per modality, a key region of ONE cache pair Kc / Vtc (the layouts of
+ * vidi_attn_cross).  Both calls read caller-owned int32 tables in DEVICE memory, 16 words per record, never written by the library:
+ *   items[n_items]  one per (segment, modality, 32-row tile, key slice): { tok0, R = ntok * G, row tile, key_start (64-aligned),
+ *                   n_keys, byte offset of the region's key mask in `mask` or -1, z, zsplit, base row of this (segment, modality)'s
+ *                   partials in Opart / ML, Rpad, 1 if the segment has a single row tile, 0... }
+ *   segs[n_segs]    one per segment: { tok0, R, Rpad, image: base row, W (= its zsplit; 0: no key), zero_out, audio: base, W, zero_out, 0... }
+ * vidi_attn_cross_seg runs the partial pass of every item in one launch of n_items x nkv blocks; a (segment, modality) with W slices
+ * owns rows [base, base + W * nkv * Rpad) of Opart:[part_rows][HD] / ML:[part_rows][2], laid out [W][nkv][Rpad] as vidi_attn_cross
+ * writes them, and its partials are bit-identical to that call's on the segment alone.  vidi_attn_merge_seg merges every (row, kv head)
+ * of both modalities in one launch into OutImg / OutAud:[n_tokens, ldo] (either may be null; W == 0 or zero_out writes zeros,
+ * gemma.py:180-192); max_rows = the largest R.  A record that does not fit n_tokens / ntile64 / mask_len / part_rows is skipped. */
+int vidi_attn_cross_seg(const void* Q, const void* Kc, const void* Vtc, const void* mask, long long mask_len, float* Opart, float* ML,
+                        long long part_rows, const int* items, int n_items, int n_tokens, int G, int nkv, int HD, int ldq, int ntile64,
+                        float scale, float softcap, int dtype, void* stream);
+int vidi_attn_merge_seg(const float* Opart, const float* ML, long long part_rows, const int* segs, int n_segs, int max_rows,
+                        void* OutImg, void* OutAud, int n_tokens, int nkv, int G, int HD, int ldo, int dtype, void* stream);
 
 /* Text causal self-attention with softcap / sliding window / key mask (gemma.py:165-175 ->
  * TP gemma2:248-288 under FA2) over the text KV cache [B,Lmax,nkv*HD]. */

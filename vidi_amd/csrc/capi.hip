@@ -372,6 +372,24 @@ int vidi_attn_merge2_sharded(const float* OpartA, const float* MLA, long long ws
     return vidi_attn_merge2_dispatch(a, b, HD, dtype, (hipStream_t)stream);
 }
 
+int vidi_attn_cross_seg(const void* Q, const void* Kc, const void* Vtc, const void* mask, long long mask_len, float* Opart, float* ML,
+                        long long part_rows, const int* items, int n_items, int n_tokens, int G, int nkv, int HD, int ldq, int ntile64,
+                        float scale, float softcap, int dtype, void* stream) {
+    (void)hipGetLastError();
+    if (!Q || !Kc || !Vtc || !Opart || !ML || !items) return VIDI_ERR_ARG;
+    return vidi_attn_cross_seg_dispatch(Q, Kc, Vtc, mask, mask_len, Opart, ML, part_rows, items, n_items, n_tokens, G, nkv, HD, ldq, ntile64,
+                                        scale, softcap, dtype, (hipStream_t)stream);
+}
+
+int vidi_attn_merge_seg(const float* Opart, const float* ML, long long part_rows, const int* segs, int n_segs, int max_rows,
+                        void* OutImg, void* OutAud, int n_tokens, int nkv, int G, int HD, int ldo, int dtype, void* stream) {
+    (void)hipGetLastError();
+    if (!Opart || !ML || !segs || (!OutImg && !OutAud)) return VIDI_ERR_ARG;
+    if (HD != 256 && HD != 128) return VIDI_ERR_SHAPE;
+    return vidi_attn_merge_seg_dispatch(Opart, ML, part_rows, segs, n_segs, max_rows, OutImg, OutAud, n_tokens, nkv, G, HD, ldo, dtype,
+                                        (hipStream_t)stream);
+}
+
 int vidi_attn_text(const void* Q, const void* Kc, const void* Vc, const void* kmask, void* O,
                    int B, int Lq, int Lmax, int nq, int nkv, int HD, int past_len, int window,
                    float scale, float softcap, int dtype, void* stream) {

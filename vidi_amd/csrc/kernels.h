@@ -134,6 +134,11 @@ int vidi_attn_cross_dispatch(const AttnCrossParams& p, int HD, int zsplit, int d
 int vidi_attn_cross2_dispatch(const AttnCrossParams& a, const AttnCrossParams& b, int HD, int za, int zb, int dtype, hipStream_t st);
 int vidi_attn_merge_dispatch(const AttnMergeParams& p, int HD, int dtype, hipStream_t st);
 int vidi_attn_merge2_dispatch(const AttnMergeParams& a, const AttnMergeParams& b, int HD, int dtype, hipStream_t st);
+int vidi_attn_cross_seg_dispatch(const void* Q, const void* Kc, const void* Vtc, const void* mask, long long mask_len, float* Opart, float* ML,
+                                 long long part_rows, const int* items, int n_items, int n_tokens, int G, int nkv, int HD, int ldq, int ntile64,
+                                 float scale, float softcap, int dtype, hipStream_t st);                                  // attn_cross_seg.hip
+int vidi_attn_merge_seg_dispatch(const float* Opart, const float* ML, long long part_rows, const int* segs, int n_segs, int max_rows,
+                                 void* OutImg, void* OutAud, int n_tokens, int nkv, int G, int HD, int ldo, int dtype, hipStream_t st);
 int vidi_attn_text_dispatch(const AttnTextParams& p, int HD, int dtype, hipStream_t st);
 int vidi_attn_text_decode_dispatch(const void* qkv, int ldqkv, void* Kc, void* Vc, const void* kmask, const void* cs, const void* sn,
                                    void* O, int B, int Lmax, int nq, int nkv, int HD, int pos0, const int* pos_dev, int window,

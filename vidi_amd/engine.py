@@ -30,6 +30,7 @@ from __future__ import annotations
 import math
 import os
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -42,7 +43,7 @@ def _round_up(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
 
-from .shard import audio_token_counts, token_budget_hw  # noqa: E402,F401  (host integer rules; re-exported: bench.py and the tests import them from here)
+from .shard import audio_token_counts, single_key_slices, token_budget_hw  # noqa: E402,F401  (host integer rules; re-exported: bench.py and the tests import them from here)
 
 
 @dataclass
@@ -66,6 +67,31 @@ class MMState:
     image_attention_mask: Optional[torch.Tensor] = None
     audio_features: Optional[torch.Tensor] = None
     audio_attention_mask: Optional[torch.Tensor] = None
+
+
+@dataclass
+class MMBatchState:
+    """The resident state of a BATCH of different videos (one per text row): every video's `[image | pad | audio | pad]` key region at
+    a 64-aligned offset of ONE kc / vtc allocation.  `videos[b]` holds video b's counts, region starts (absolute key positions),
+    `*_any_valid` flags and whether it carries a key mask; `mask` is one uint8 buffer laid out like the key axis of the caches (None when
+    every key of every video is valid).  Consumed by `text_forward` through the segmented cross-attention (vidi_attn_cross_seg)."""
+    videos: List[MMState]
+    ntile64: int = 0
+    kc: Optional[torch.Tensor] = None        # [L, nkv, ntile64, 64, hd]
+    vtc: Optional[torch.Tensor] = None       # [L, nkv, 2*ntile64, hd, 32]
+    mask: Optional[torch.Tensor] = None      # uint8 [ntile64 * 64]
+    g_img: int = 0                           # keys of the whole batch per modality
+    g_aud: int = 0
+    # reference-facing padded views (encode_videos outputs: [B, max N, H] / bool [B, max N])
+    image_features: Optional[torch.Tensor] = None
+    image_attention_mask: Optional[torch.Tensor] = None
+    audio_features: Optional[torch.Tensor] = None
+    audio_attention_mask: Optional[torch.Tensor] = None
+    plans: Optional[dict] = None             # tokens per video -> (plan, device tables, workspaces): built once per prefill / decode loop
+
+    @property
+    def n_videos(self) -> int:
+        return len(self.videos)
 
 
 @dataclass
@@ -640,6 +666,33 @@ class VidiEngine:
                     hip.scale(src.contiguous(), X[off: off + n], self.normalizer)
         st.kc = torch.empty((Lr, nkv, ntile, 64, hd), dtype=self.dtype, device=self.dev)
         st.vtc = torch.empty((Lr, nkv, 2 * ntile, hd, 32), dtype=self.dtype, device=self.dev)
+        self._mm_stream_layers(X, st.kc, st.vtc, ntot, ntile)
+        if check_masks:
+            # one host sync per VIDEO (the reference syncs per layer per step: xattn.py:214-215)
+            for name, m in (("img", img_mask), ("aud", aud_mask)):
+                if m is None and not self.sharded:
+                    continue
+                nv = int(m.sum().item()) if m is not None and m.numel() else 0
+                nv_global = nv
+                if self.sharded:                       # "sample has any valid key" is a global property
+                    import torch.distributed as dist
+                    t = torch.tensor([nv], dtype=torch.int64, device=self.dev if dist.get_backend(self.pg) != "gloo" else "cpu")
+                    dist.all_reduce(t, group=self.pg)
+                    nv_global = int(t.item())
+                setattr(st, f"{name}_any_valid", nv_global > 0)
+                if m is not None and 0 < nv < m.numel() or (m is not None and nv == 0 and m.numel() > 0 and nv_global > 0):
+                    pad = torch.zeros(_round_up(m.numel(), 64), dtype=torch.uint8, device=self.dev)
+                    pad[: m.numel()] = m
+                    setattr(st, f"{name}_mask", pad)
+        return st
+
+    def _mm_stream_layers(self, X: torch.Tensor, kc: torch.Tensor, vtc: torch.Tensor, ntot: int, ntile: int) -> None:
+        """the diagonal stream of `ntot` rows (one video, or the concatenated regions of a batch: every launch is row-wise) through all
+        layers, filling the cross-attention caches"""
+        cfg = self.cfg
+        H, nkv, hd, G = cfg.hidden_size, cfg.num_key_value_heads, cfg.head_dim, cfg.num_attention_heads // cfg.num_key_value_heads
+        kvd = nkv * hd
+        Lr = cfg.num_hidden_layers
         hbuf = self._buf("mm_h", (ntot, H))
         vrow = self._buf("mm_vrow", (ntot, kvd))
         u = self._buf("mm_u", (ntot, H))
@@ -652,7 +705,7 @@ class VidiEngine:
                 pr["stream_x"].append(X.index_select(0, pr["stream_rows"]))
             if not fused or li == 0:                                                                 # fused: produced by the previous layer's second pass
                 hip.norm(self.norm_mode, X, L["ln_in"], eps=eps, out=hbuf)                           # gemma.py:183-184 / mistral.py:204-205
-            hip.gemm_kv_cache(hbuf, L["wkv"], st.kc[li], st.vtc[li], vrow, kvd=kvd, hd=hd, ntile64=ntile, tok0=0)   # :61-63
+            hip.gemm_kv_cache(hbuf, L["wkv"], kc[li], vtc[li], vrow, kvd=kvd, hd=hd, ntile64=ntile, tok0=0)   # :61-63
             if li == Lr - 1:
                 break                                                                                # dead update on the last layer
             if self.mistral:
@@ -682,24 +735,55 @@ class VidiEngine:
                 hip.resid_norm2(u, None, None, X, L["ln_post_ffn"], self.layers[li + 1]["ln_in"], X, hbuf, eps=eps)   # :120-121 + next :183
             else:
                 hip.norm(hip.NORM_GEMMA_ADD, u, L["ln_post_ffn"], eps=eps, residual=X, out=X)        # :120-121
-        if check_masks:
-            # one host sync per VIDEO (the reference syncs per layer per step: xattn.py:214-215)
-            for name, m in (("img", img_mask), ("aud", aud_mask)):
-                if m is None and not self.sharded:
-                    continue
-                nv = int(m.sum().item()) if m is not None and m.numel() else 0
-                nv_global = nv
-                if self.sharded:                       # "sample has any valid key" is a global property
-                    import torch.distributed as dist
-                    t = torch.tensor([nv], dtype=torch.int64, device=self.dev if dist.get_backend(self.pg) != "gloo" else "cpu")
-                    dist.all_reduce(t, group=self.pg)
-                    nv_global = int(t.item())
-                setattr(st, f"{name}_any_valid", nv_global > 0)
-                if m is not None and 0 < nv < m.numel() or (m is not None and nv == 0 and m.numel() > 0 and nv_global > 0):
-                    pad = torch.zeros(_round_up(m.numel(), 64), dtype=torch.uint8, device=self.dev)
-                    pad[: m.numel()] = m
-                    setattr(st, f"{name}_mask", pad)
-        return st
+
+    def mm_stream_prefill_batch(self, per: List[Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]],
+                                pre_normalized: bool = True) -> MMBatchState:
+        """`per[b]` = (img, img_mask, aud, aud_mask) of video b as `mm_stream_prefill` takes them.  The diagonal stream is row-wise, so the
+        whole batch runs through the layers ONCE over the concatenated rows `[image_0 | pad | audio_0 | pad | image_1 | ...]` (pad rows are
+        zero rows, as the pad between image and audio of one video is) and fills one cache pair; `videos[b]` of the result is a full
+        `MMState` of video b that aliases its region of the shared caches.  One host sync for all the masks of the batch."""
+        if self.sharded or self.world > 1:
+            raise RuntimeError("a batch of different videos is decoded on one GPU (the sharded modes take one video)")
+        cfg = self.cfg
+        H, nkv, hd = cfg.hidden_size, cfg.num_key_value_heads, cfg.head_dim
+        Lr = cfg.num_hidden_layers
+        videos, off = [], 0
+        for img, _, aud, _ in per:
+            n_img = 0 if img is None else int(img.shape[0])
+            n_aud = 0 if aud is None else int(aud.shape[0])
+            v = MMState(n_img=n_img, n_aud=n_aud, img_start=off, aud_start=off + _round_up(n_img, 64))
+            v.g_img, v.g_aud = n_img, n_aud
+            off = v.aud_start + _round_up(n_aud, 64)
+            videos.append(v)
+        ntot, ntile = off, off // 64
+        bs = MMBatchState(videos=videos, ntile64=ntile, g_img=sum(v.n_img for v in videos), g_aud=sum(v.n_aud for v in videos), plans={})
+        if ntot == 0:
+            return bs
+        X = torch.zeros((ntot, H), dtype=self.dtype, device=self.dev)
+        for v, (img, _, aud, _) in zip(videos, per):
+            for src, o, n in ((img, v.img_start, v.n_img), (aud, v.aud_start, v.n_aud)):
+                if n:
+                    if pre_normalized:
+                        X[o: o + n].copy_(src)
+                    else:
+                        hip.scale(src.contiguous(), X[o: o + n], self.normalizer)
+        bs.kc = torch.empty((Lr, nkv, ntile, 64, hd), dtype=self.dtype, device=self.dev)
+        bs.vtc = torch.empty((Lr, nkv, 2 * ntile, hd, 32), dtype=self.dtype, device=self.dev)
+        self._mm_stream_layers(X, bs.kc, bs.vtc, ntot, ntile)
+        masks = [(v, name, m) for v, (_, mi, _, ma) in zip(videos, per) for name, m in (("img", mi), ("aud", ma)) if m is not None and m.numel()]
+        if masks:
+            counts = torch.stack([m.sum() for _, _, m in masks]).tolist()
+            for (v, name, m), nv in zip(masks, counts):
+                setattr(v, f"{name}_any_valid", nv > 0)
+                if 0 < nv < m.numel():
+                    if bs.mask is None:
+                        bs.mask = torch.ones(ntot, dtype=torch.uint8, device=self.dev)
+                    o = getattr(v, f"{name}_start")
+                    bs.mask[o: o + m.numel()] = m
+                    setattr(v, f"{name}_mask", bs.mask[o: o + _round_up(m.numel(), 64)])
+        for v in videos:
+            v.ntile64, v.kc, v.vtc = ntile, bs.kc, bs.vtc
+        return bs
 
     # -----------------------------------------------------------------------------------------
     # text stream
@@ -748,7 +832,7 @@ class VidiEngine:
         Rpad = _round_up(R, 32)
         nsub = (n + 31) // 32
         row_blocks = -(-(Rpad // 32) // hip.attn_cross_row_tiles_per_block(Rpad, cfg.attn_logit_softcapping, self.dtype))      # blocks along the rows (a block covers 1 or 4 row tiles)
-        zsplit = max(1, min(256 // max(1, nkv * row_blocks), (nsub + 7) // 8))
+        zsplit = single_key_slices(256 // max(1, nkv * row_blocks), nsub)
         key = f"xattn_ws_{which}_{zsplit}_{Rpad}"        # one workspace per modality: both partial sets live until the merge
         if key not in self._ws:
             with torch.inference_mode(False):
@@ -804,6 +888,52 @@ class VidiEngine:
             return merge
         hip.attn_merge2(*merge[0], *merge[1], nkv=nkv, R=R, Rpad=Rpad, G=G, HD=hd)
         return True
+
+    def _cross_plan(self, mm: MMBatchState, ntoks: List[int]):
+        """plan, device tables and partial workspaces of the segmented cross-attention for `ntoks[b]` packed query tokens of video b; kept
+        on the state, so a prefill and a decode loop build theirs once (not per layer or per step)"""
+        from .shard import CrossSegment, plan_cross_segments
+        key = tuple(int(n) for n in ntoks)
+        if mm.plans is None:
+            mm.plans = {}
+        ent = mm.plans.get(key)
+        if ent is not None:
+            return ent
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the segment tables of a batch of videos cannot be built during graph capture")
+        cfg = self.cfg
+        nkv, hd = cfg.num_key_value_heads, cfg.head_dim
+        segs, tok0 = [], 0
+        for v, nt in zip(mm.videos, key):
+            segs.append(CrossSegment(tok0=tok0, ntok=nt,
+                                     img_start=v.img_start, n_img=v.n_img, img_mask=v.img_start if v.img_mask is not None else -1,
+                                     img_zero=not v.img_any_valid,
+                                     aud_start=v.aud_start, n_aud=v.n_aud, aud_mask=v.aud_start if v.aud_mask is not None else -1,
+                                     aud_zero=not v.aud_any_valid))
+            tok0 += nt
+        plan = plan_cross_segments(segs, nkv, cfg.num_attention_heads // nkv, hd)
+        with torch.inference_mode(False):
+            items = torch.tensor(plan.items if plan.items else [[0] * 16], dtype=torch.int32).to(self.dev)
+            seg_t = torch.tensor(plan.segs, dtype=torch.int32).to(self.dev)
+            opart = torch.empty((plan.part_rows, hd), dtype=torch.float32, device=self.dev)
+            ml = torch.empty((plan.part_rows, 2), dtype=torch.float32, device=self.dev)
+        while len(mm.plans) >= 4:                         # a prefill's and a decode loop's plan at a time; older ones (other prompt lengths) go
+            mm.plans.pop(next(iter(mm.plans)))
+        ent = mm.plans[key] = SimpleNamespace(plan=plan, items=items, segs=seg_t, opart=opart, ml=ml, n_tokens=tok0)
+        return ent
+
+    def _cross_seg(self, q: torch.Tensor, li: int, mm: MMBatchState, out_img: Optional[torch.Tensor], out_aud: Optional[torch.Tensor], ent):
+        """T2V + T2A of one layer for a batch of different videos: ONE split-KV launch over every (video, modality) key region
+        (vidi_attn_cross_seg) and ONE merge launch (vidi_attn_merge_seg); a video without keys of a modality gets zeros for it"""
+        cfg = self.cfg
+        nkv, hd = cfg.num_key_value_heads, cfg.head_dim
+        G = cfg.num_attention_heads // nkv
+        plan = ent.plan
+        for (i0, n), keys in zip(plan.launches, plan.launch_keys):
+            hip.attn_cross_seg(q, mm.kc[li], mm.vtc[li], mm.mask, ent.opart, ent.ml, ent.items[i0:], n_items=n, n_keys=keys, G=G, nkv=nkv, HD=hd,
+                               ntile64=mm.ntile64, scale=cfg.query_pre_attn_scalar ** -0.5, softcap=cfg.attn_logit_softcapping)
+        hip.attn_merge_seg(ent.opart, ent.ml, ent.segs, out_img, out_aud, n_segs=len(plan.segs), max_rows=plan.max_rows,
+                           n_tokens=ent.n_tokens, nkv=nkv, G=G, HD=hd)
 
     def _cross_sharded_begin(self, q: torch.Tensor, li: int, mm: MMState, outs: Dict[str, torch.Tensor], R: int, async_op: bool = False):
         """T2V + T2A of one layer with the keys sharded over ranks, first half.  Per rank: split-KV partials over the local
@@ -910,6 +1040,11 @@ class VidiEngine:
             ts.kmask[:, p0: p0 + Lq] = 1
         else:
             ts.kmask[:, p0: p0 + Lq] = new_mask.to(torch.uint8)
+        batch = isinstance(mm, MMBatchState)                 # one video per text row (or per `B / videos` consecutive rows)
+        if batch and (self.sharded or dyn):
+            raise RuntimeError("a batch of different videos runs eagerly on one GPU: no sharded mode, no graph-captured decode")
+        if batch and B % mm.n_videos:
+            raise ValueError(f"{B} text rows over {mm.n_videos} videos: every video takes the same number of consecutive rows")
         has_img = mm is not None and mm.g_img > 0
         has_aud = mm is not None and mm.g_aud > 0
         nstream = 1 + int(has_img) + int(has_aud)
@@ -931,6 +1066,16 @@ class VidiEngine:
                 att_pad = self._buf("t_att_pad", (Mp, nqd))
             else:
                 rows_map = None
+        xplan = None
+        if batch and (has_img or has_aud):
+            # rows of video b = the packed rows of its text rows, contiguous and in order; the plan is looked up once per call and built once
+            # per prefill / decode loop (it depends on the token counts alone)
+            rep = B // mm.n_videos
+            per_row = torch.bincount(rows_map // Lq, minlength=B).tolist() if rows_map is not None else [Lq] * B
+            ntoks = [sum(per_row[b * rep: (b + 1) * rep]) for b in range(mm.n_videos)]
+            if min(ntoks) <= 0:
+                raise ValueError("every video of the batch needs at least one attended text token")
+            xplan = self._cross_plan(mm, ntoks)
         hn = self._buf("t_h", (M, H))
         qkv = self._buf("t_qkv", (M, nqd + 2 * kvd))
         qr = self._buf("t_qr", (M, nqd))
@@ -964,7 +1109,7 @@ class VidiEngine:
                           pos_dev=ts.pos_dev if dyn else None)
             # decode with both modalities on one GPU: the T2T launch is held back and issued together with the merge of the
             # cross-attention partials (vidi_attn_text_decode_merge2) after the T2V + T2A partial pass
-            t2t_with_merge = (t2t_fused and self.decode_tail and self.cross_dual and not self.sharded and hd in (128, 256)
+            t2t_with_merge = (t2t_fused and self.decode_tail and self.cross_dual and not self.sharded and not batch and hd in (128, 256)
                               and mm is not None and mm.g_img > 0 and mm.g_aud > 0)
             k = 1
             pending = outs = None
@@ -1007,6 +1152,10 @@ class VidiEngine:
                     self._cross_sharded_finish(pending)
                 elif outs:
                     self._cross_sharded(qraw, li, mm, outs, R=M * G)
+            elif batch:
+                if xplan is not None:
+                    self._cross_seg(qraw, li, mm, att[M: 2 * M] if has_img else None,
+                                    att[(1 + int(has_img)) * M: (2 + int(has_img)) * M] if has_aud else None, xplan)
             else:
                 both = has_img and has_aud
                 pend = []
@@ -1110,6 +1259,8 @@ class VidiEngine:
         one token per call.  Sharded (one process per GPU): the per-layer all-gathers of the partials are RCCL launches on the
         capture stream, so the whole step — 42 exchanges included — is one graph launch per token; the gloo test transport moves
         the partials through the host and cannot be captured."""
+        if isinstance(mm, MMBatchState):
+            raise RuntimeError("graph-captured decode takes one video (a batch of different videos decodes eagerly)")
         if self.sharded:
             import torch.distributed as dist
             if dist.get_backend(self.pg) != "nccl":

@@ -54,6 +54,8 @@ SIGNATURES = {
     "vidi_attn_merge2": [_c_vp] * 3 + [_c_int] * 2 + [_c_vp] * 3 + [_c_int] * 2 + [_c_int] * 7 + [_c_vp],
     "vidi_attn_merge2_sharded": ([_c_vp] * 2 + [_c_ll] * 2 + [_c_vp] * 3 + [_c_int] * 2) * 2 + [_c_int] * 8 + [_c_vp],
     "vidi_attn_cross2": [_c_vp] * 3 + ([_c_vp] * 3 + [_c_int] * 3) * 2 + [_c_int] * 7 + [_c_f, _c_f, _c_int, _c_vp],
+    "vidi_attn_cross_seg": [_c_vp] * 4 + [_c_ll] + [_c_vp] * 2 + [_c_ll, _c_vp] + [_c_int] * 7 + [_c_f, _c_f, _c_int, _c_vp],
+    "vidi_attn_merge_seg": [_c_vp] * 2 + [_c_ll, _c_vp, _c_int, _c_int, _c_vp, _c_vp] + [_c_int] * 6 + [_c_vp],
     "vidi_attn_text_decode": [_c_vp, _c_int] + [_c_vp] * 6 + [_c_int] * 6 + [_c_vp, _c_int, _c_f, _c_f, _c_int, _c_vp],
     "vidi_attn_text_decode_merge2": [_c_vp, _c_int] + [_c_vp] * 6 + [_c_int] * 6 + [_c_vp, _c_int, _c_f, _c_f] +
                                     ([_c_vp] * 3 + [_c_int] * 2) * 2 + [_c_int] * 4 + [_c_vp],
@@ -212,9 +214,10 @@ class _Timed:
     def __init__(self, fn, name):
         self.fn, self.name = fn, name
 
-    def __call__(self, *a):
+    def __call__(self, *a, work=None):
+        """`work`: (family, algorithmic work, unit) from a wrapper whose launch reads its sizes from device memory (else `_work(name, a)`)"""
         t = TIMER
-        rc = self.fn(*a) if t is None else t.run(self.name, a, self.fn)
+        rc = self.fn(*a) if t is None else t.run(self.name, a, self.fn, *(() if work is None else (work,)))
         if AFTER_CALL is not None:
             AFTER_CALL(self.name)
         return rc
@@ -227,8 +230,8 @@ class KernelTimer:
     def __init__(self):
         self.rec = []
 
-    def run(self, name, a, fn):
-        fam, work, unit = _work(name, a)
+    def run(self, name, a, fn, stated=None):
+        fam, work, unit = _work(name, a) if stated is None else stated
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         rc = fn(*a)
@@ -634,6 +637,24 @@ def attn_merge2(opart_a, ml_a, out_a, W_a, zero_a, opart_b, ml_b, out_b, W_b, ze
     assert out_a.stride(0) == out_b.stride(0)
     _check(lib.vidi_attn_merge2(_p(opart_a), _p(ml_a), _p(out_a), W_a, 1 if zero_a else 0, _p(opart_b), _p(ml_b), _p(out_b), W_b,
                                 1 if zero_b else 0, nkv, R, Rpad, G, HD, out_a.stride(0), _dt(out_a), _stream()), "vidi_attn_merge2")
+
+
+def attn_cross_seg(q, kc, vtc, mask, opart, ml, items, *, n_items, G, nkv, HD, ntile64, scale, softcap, n_keys=0):
+    """split-KV partial pass of a batch of videos in one launch; `items`: int32 device table of shard.plan_cross_segments; `n_keys`: the
+    keys the launch sweeps (plan.launch_keys), for KernelTimer's byte model only — the table lives on the device"""
+    lib = load_library()
+    _check(lib.vidi_attn_cross_seg(_p(q), _p(kc), _p(vtc), _p(mask), 0 if mask is None else mask.numel(), _p(opart), _p(ml), opart.shape[0],
+                                   _p(items), n_items, q.shape[0], G, nkv, HD, q.stride(0), ntile64, float(scale), float(softcap or 0.0),
+                                   _dt(q), _stream(), work=("attn_cross", float(n_keys) * 2 * nkv * HD * 2, "byte")), "vidi_attn_cross_seg")
+
+
+def attn_merge_seg(opart, ml, segs, out_img, out_aud, *, n_segs, max_rows, n_tokens, nkv, G, HD):
+    """merge of every segment's partials of both modalities in one launch; `segs`: int32 device table of shard.plan_cross_segments"""
+    lib = load_library()
+    ref = out_img if out_img is not None else out_aud
+    assert out_img is None or out_aud is None or out_img.stride(0) == out_aud.stride(0)
+    _check(lib.vidi_attn_merge_seg(_p(opart), _p(ml), opart.shape[0], _p(segs), n_segs, max_rows, _p(out_img), _p(out_aud), n_tokens, nkv, G,
+                                   HD, ref.stride(0), _dt(ref), _stream()), "vidi_attn_merge_seg")
 
 
 def attn_merge2_sharded(sets, *, nkv, R, Rpad, rpo, G, HD, ldo, dtype):

@@ -21,7 +21,7 @@ from typing import Any, Dict, Optional, Sequence, Tuple
 import torch
 
 from .config import VidiConfig
-from .engine import MMState, VidiEngine
+from .engine import MMBatchState, MMState, VidiEngine
 
 IGNORE_INDEX = -100
 IMAGE_TOKEN_INDEX = -200
@@ -317,6 +317,61 @@ class VidiForCausalLM:
         st.image_attention_mask, st.audio_attention_mask = mi, ma
         return st
 
+    def _batch_path(self, num_beams: int = 1) -> bool:
+        """a batch with one video per row goes through ONE decoder pass (the segmented cross-attention) unless the call needs what only the
+        row-by-row path has: beams, a sharded engine, an engine without the batch entry points — or VIDI_MULTI_VIDEO=0, the A/B arm"""
+        eng = self.engine
+        return (os.environ.get("VIDI_MULTI_VIDEO", "1") != "0" and num_beams == 1 and eng.world == 1 and not self._shard_on()
+                and hasattr(eng, "mm_stream_prefill_batch"))
+
+    def encode_mm_batch(self, images, audios, audio_sizes) -> MMBatchState:
+        """`encode_mm_state` for a batch with one video per row: both towers once over the batch and the batch-wide token budget
+        (multimodal.py:157-180, as `encode_videos`), every video finished on its own (positions, norms, masks), then the diagonal stream
+        ONCE over all the videos' tokens into one cache pair.  The result stays valid across calls (`mm_state=`): the resident state of
+        the batch."""
+        eng = self.engine
+        B = self._n_videos(images, audios)
+        vis, aud = self._tower_batch(images, audios)
+        budget = self._batch_frames(images)
+        nz = eng.normalizer
+        per = []
+        for i in range(B):
+            img = self._single(self._row(images, i), "images")
+            au = self._single(self._row(audios, i), "audios")
+            fi = mi = fa = ma = None
+            if img is not None:
+                kw = {} if budget is None else dict(budget_frames=int(budget))
+                if vis is not None:
+                    kw["vis_features"] = vis[i]
+                fi, mi = eng.encode_video_images(img.to(eng.dev), normalizer=nz, **kw)
+            if au is not None:
+                kw = {} if aud is None else dict(aud_features=aud[i])
+                fa, ma = eng.encode_video_audios(au.to(eng.dev), int(audio_sizes[i]), normalizer=nz, **kw)
+            per.append((fi, mi, fa, ma))
+        st = eng.mm_stream_prefill_batch(per, pre_normalized=True)
+        pad = torch.nn.utils.rnn.pad_sequence
+        cat = lambda k, f=(lambda t: t): None if per[0][k] is None else pad([f(p[k]) for p in per], batch_first=True)     # noqa: E731
+        st.image_features, st.image_attention_mask = cat(0), cat(1, lambda t: t.bool())
+        st.audio_features, st.audio_attention_mask = cat(2), cat(3, lambda t: t.bool())
+        for v, (fi, mi, fa, ma) in zip(st.videos, per):
+            v.image_attention_mask, v.audio_attention_mask = mi, ma
+        return st
+
+    @staticmethod
+    def _right_padded(inputs, attention_mask):
+        """rows of a padded batch with their attended tokens moved to the front (what a left-padded batch becomes; rows never interact, and
+        positions count attended tokens): -> (ids, mask) for `strip_image_token`"""
+        if attention_mask is None:
+            return inputs, None
+        ids, am = inputs.detach().cpu(), attention_mask.detach().cpu().bool()
+        out = torch.zeros_like(ids)
+        mask = torch.zeros_like(am)
+        for i in range(ids.shape[0]):
+            n = int(am[i].sum())
+            out[i, :n] = ids[i][am[i]]
+            mask[i, :n] = True
+        return out, mask
+
     # ---- process-group helpers of the sharded path ----
     def _backend(self) -> str:
         import torch.distributed as dist
@@ -433,6 +488,18 @@ class VidiForCausalLM:
             raise ValueError("You are attempting to perform batched generation with padding_side='right' this may lead to "
                              "unexpected behaviour for Flash Attention version of Mistral. Make sure to call "
                              "`tokenizer.padding_side  = 'left'` before tokenizing the input. ")
+        if mm_state is None and self._n_videos(images, audios) > 1 and self._batch_path(num_beams):
+            # one video PER ROW, decoded together: one encode of the batch, then the ordinary loop below over all rows
+            assert inputs.shape[0] == self._n_videos(images, audios), "one prompt per video"
+            mm_state = self.encode_mm_batch(images, audios, audio_sizes)
+        if isinstance(mm_state, MMBatchState):
+            if not self._batch_path(num_beams):
+                raise NotImplementedError("a resident multi-video state takes one beam on one GPU (and not VIDI_MULTI_VIDEO=0): "
+                                          "pass images= / audios= for the row-by-row path")
+            if inputs.shape[0] != mm_state.n_videos:
+                raise ValueError(f"{inputs.shape[0]} prompts for a state of {mm_state.n_videos} videos: one prompt per video")
+            # rows never interact: a left-padded batch (what Vidi-7B demands, mistral.py:366-373) is decoded with its tokens moved to the front
+            inputs, attention_mask = self._right_padded(inputs, attention_mask)
         if mm_state is None and self._n_videos(images, audios) > 1:
             # one video PER ROW (multimodal.py:156-252 batches them with pad_sequence + masks): rows never interact, so each
             # row is answered against its own video, unpadded, and the answers are re-padded — the same tokens
@@ -526,7 +593,8 @@ class VidiForCausalLM:
         # host work).  Measured on MI355X (60-min video): replay 19.3 ms/token vs 21.0 eager, capture 126 ms —
         # it only pays for generations of ~80+ tokens, so it is opt-in; the sharded path stays eager.
         use_graph = (not do_sample and not processors and not criteria and not as_dict and max_new >= int(os.environ.get("VIDI_DECODE_GRAPH_MIN", "8"))
-                     and os.environ.get("VIDI_DECODE_GRAPH", "0") == "1" and (eng.world == 1 or self._backend() == "nccl"))
+                     and os.environ.get("VIDI_DECODE_GRAPH", "0") == "1" and (eng.world == 1 or self._backend() == "nccl")
+                     and not isinstance(mm_state, MMBatchState))           # a batch of different videos decodes eagerly
         replay = None
         if streamer is not None:
             # HF generate() hands the streamer the prompt ids first — [B, 0] when driven by inputs_embeds, as the reference is
@@ -627,6 +695,15 @@ class VidiForCausalLM:
                 images=None, audios=None, audio_sizes=None, mm_state: Optional[MMState] = None,
                 logits_to_keep: int = 0, labels: Optional[torch.Tensor] = None, **kwargs) -> DattnCausalLMOutputWithPast:
         eng = self.engine
+        if mm_state is None and self._n_videos(images, audios) > 1 and self._batch_path():
+            mm_state = self.encode_mm_batch(images, audios, audio_sizes)
+        if isinstance(mm_state, MMBatchState):
+            # one video per row through ONE decoder pass; logits in the right-padded [B, L, V] frame (pad slots hold the logits of zero rows)
+            if input_ids.shape[0] != mm_state.n_videos:
+                raise ValueError(f"{input_ids.shape[0]} prompts for a state of {mm_state.n_videos} videos: one prompt per video")
+            if labels is not None and attention_mask is not None and not bool(attention_mask[:, 0].bool().all()):
+                raise NotImplementedError("labels with a left-padded multi-video batch")
+            input_ids, attention_mask = self._right_padded(input_ids, attention_mask)
         if mm_state is None and self._n_videos(images, audios) > 1:
             # one video per row: rows are independent -> run them one by one, unpadded, and lay the logits back out in the
             # padded [B, L, V] frame of the reference (pad slots hold zeros there, unspecified values in the reference)
