@@ -52,7 +52,11 @@ const char* vidi_build_info(void);
  * batch>1 strides X/Y/R by bsX/bsY/bsR elements (W shared).  K % 64 == 0, N % 32 == 0.
  * repkv_hd/repkv_g != 0: X column for logical k is (k/(g*hd))*hd + k%hd, i.e. the GEMM consumes
  *   repeat_kv(V) without materialising it (gemma.py:77-78,96,196-197).
- * tile_cfg: -1 auto, 0 = 128x128, 1 = 128x256, 2 = 256x256, 3 = conservative register-staged.
+ * tile_cfg: -1 auto, 0 = 128x128, 1 = 128x256, 2 = 256x256, 3 = conservative register-staged (plain bias epilogue only),
+ *   4 = 256x256 with 8 waves x (128x64) and the 16x16x32 MFMA, 5 = the persistent 4-wave kernel (256x256 tiles, or 288x224 at the widths
+ *   that are multiples of 288 but not of 256; K >= 192; VIDI_ERR_ARG for an epilogue combination it lacks), 11 = 192x256 (plain GEMM
+ *   only).  Auto picks 5 from 192 tiles of 256x256 up where the kernel has the epilogue, else 4, and 0 below; the folded LayerNorm
+ *   (vidi_gemm_ln*) runs on 0 and 5 only.  The whole rule is vidi_amd/csrc/gemm_route.h; tools/gemm_route_dump.hip prints it per call.
  * Replaces: SigLIP q/k/v/out/fc1/fc2 + patch-embed conv (TP/models/siglip/modeling_siglip.py:124-130,
  * 250-357), Whisper convs/linears (TP/models/whisper/modeling_whisper.py:566-567,279-282,375-376),
  * projector MLP (model/mm_layer/mlp.py:9-28), Conv1d audio pool (multimodal.py:85-88,232),

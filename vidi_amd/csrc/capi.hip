@@ -1,5 +1,6 @@
 // extern "C" entry points of libvidi_hip.so (declared in include/vidi_hip.h).
 #include "kernels.h"
+#include "gemm_route.h"
 #include "attn_text_decode.h"
 #include "gemm_skinny_api.h"
 #include "gemv_mfma_api.h"
@@ -91,7 +92,6 @@ int vidi_gemm_geglu(const void* X, const void* Wgu, void* Y, int M, int I, int K
     if (!X || !Wgu || !Y) return VIDI_ERR_ARG;
     if (I % 32) return VIDI_ERR_SHAPE;
     GemmParams p = base_params(X, Wgu, nullptr, Y, nullptr, M, 2 * I, K, ldx, ldw, ldy, 0, 0);
-    if (tile_cfg == 3) return VIDI_ERR_ARG;
     return vidi_gemm_dispatch(p, 1, MODE_GEGLU, 0, tile_cfg, dtype, (hipStream_t)stream);
 }
 
@@ -103,7 +103,6 @@ int vidi_gemm_glu(const void* X, const void* Wgu, void* Y, int M, int I, int K, 
     if (act != ACT_GELU_TANH && act != ACT_SILU) return VIDI_ERR_ARG;
     GemmParams p = base_params(X, Wgu, nullptr, Y, nullptr, M, 2 * I, K, ldx, ldw, ldy, 0, 0);
     p.act = act;
-    if (tile_cfg == 3) return VIDI_ERR_ARG;
     return vidi_gemm_dispatch(p, 1, MODE_GEGLU, 0, tile_cfg, dtype, (hipStream_t)stream);
 }
 
@@ -116,7 +115,6 @@ int vidi_gemm_qkv_vt(const void* X, const void* W, const void* bias, void* Yqk, 
     if ((N - vstart) != nheads * hd) return VIDI_ERR_SHAPE;
     GemmParams p = base_params(X, W, bias, Yqk, nullptr, M, N, K, ldx, ldw, ldy, 0, 0);
     p.vstart = vstart; p.hd = hd; p.seq = seq; p.seqpad = seqpad; p.nheads = nheads; p.Vt = (u16*)Vt;
-    if (tile_cfg == 3) return VIDI_ERR_ARG;
     return vidi_gemm_dispatch(p, 1, MODE_QKV_VT, 0, tile_cfg, dtype, (hipStream_t)stream);
 }
 
@@ -132,20 +130,8 @@ int vidi_gemm_res_stats(const void* X, const void* W, const void* bias, void* Y,
     if (!X || !W || !bias || !Y || !R || !part) return VIDI_ERR_ARG;
     if ((ldr % 8) || ((uintptr_t)part & 7)) return VIDI_ERR_ALIGN;
     GemmParams p = base_params(X, W, bias, Y, R, M, N, K, ldx, ldw, ldy, ldr, 0);
-    const long long t256 = (long long)((N + 255) / 256) * ((M + 255) / 256);
-    const int strips = vidi_w4n_stat_strips(N);               // entries per row of `part`: a function of N alone, whichever kernel runs
-    if ((tile_cfg < 0 || tile_cfg == 5) && t256 >= 192 && K % 64 == 0 && K >= 192) {
-        p.stat_part = part;                                   // fused: the persistent kernel's epilogue emits the partial sums
-        if (strips == (N + 127) / 128) return vidi_gemm_dispatch(p, 1, MODE_PLAIN, 0, 5, dtype, (hipStream_t)stream);
-        // widths of the 288 x 224 geometry (N = 1 152): its kernel, or — if it cannot take this call — the unfused form below
-        const int rc = vidi_w4n_bias_res(p, dtype, (hipStream_t)stream);
-        if (rc != -100) return rc;
-        p.stat_part = nullptr;
-    }
-    // small problems run on a tile kernel without the fused emission: same partials from one pass over the stored rows
-    const int rc = vidi_gemm_dispatch(p, 1, MODE_PLAIN, 0, tile_cfg == 5 ? -1 : tile_cfg, dtype, (hipStream_t)stream);
-    if (rc != 0) return rc;
-    return vidi_row_partials_dispatch(Y, part, M, N, ldy, strips, dtype, (hipStream_t)stream);
+    p.stat_part = part;        // the route fuses the partial sums into the persistent kernel's epilogue, or runs one pass over the stored rows after a tile kernel
+    return vidi_gemm_dispatch(p, 1, MODE_PLAIN, 0, tile_cfg, dtype, (hipStream_t)stream);
 }
 
 size_t vidi_gemm_skinny_workspace_bytes(int M, int N, int K) {
@@ -164,13 +150,13 @@ int vidi_gemm_skinny(const void* X, const void* W, const void* bias, void* Y, vo
     return rc == -100 ? VIDI_ERR_SHAPE : rc;
 }
 
-int vidi_stat_strips(int N) { return N > 0 ? vidi_w4n_stat_strips(N) : 0; }
+int vidi_stat_strips(int N) { return N > 0 ? gemm_stat_strips(N, gemm_env()) : 0; }
 
 int vidi_ln_finalize(const float* part, float* stats, long long rows, int N, float eps, void* stream) {
     (void)hipGetLastError();
     if (!part || !stats) return VIDI_ERR_ARG;
     if (((uintptr_t)part & 7) || ((uintptr_t)stats & 7)) return VIDI_ERR_ALIGN;
-    return vidi_ln_finalize_dispatch(part, stats, rows, vidi_w4n_stat_strips(N), N, eps, (hipStream_t)stream);
+    return vidi_ln_finalize_dispatch(part, stats, rows, gemm_stat_strips(N, gemm_env()), N, eps, (hipStream_t)stream);
 }
 
 int vidi_gemm_ln(const void* X, const void* Wf, const float* stats, const float* colsum, const float* shift, void* Y,
@@ -181,7 +167,6 @@ int vidi_gemm_ln(const void* X, const void* Wf, const float* stats, const float*
     if (act != ACT_NONE && act != ACT_GELU_TANH && act != ACT_GELU_ERF) return VIDI_ERR_ARG;
     GemmParams p = base_params(X, Wf, nullptr, Y, nullptr, M, N, K, ldx, ldw, ldy, 0, 0);
     p.act = act; p.ln_stats = stats; p.ln_s = colsum; p.ln_c = shift;
-    if (tile_cfg == 3) return VIDI_ERR_ARG;
     return vidi_gemm_dispatch(p, 1, MODE_PLAIN, 0, tile_cfg, dtype, (hipStream_t)stream);
 }
 
@@ -195,7 +180,6 @@ int vidi_gemm_ln_heads(const void* X, const void* Wf, const float* stats, const 
     GemmParams p = base_params(X, Wf, nullptr, Y, nullptr, M, N, K, ldx, ldw, N, 0, 0);
     p.ln_stats = stats; p.ln_s = colsum; p.ln_c = shift;
     p.hm_seq = seq; p.hm_hd = hd; p.hm_heads = N / (3 * hd); p.hm_magic = (unsigned)((1ull << 32) / (unsigned)seq) + 1u;
-    if (tile_cfg == 3) return VIDI_ERR_ARG;
     return vidi_gemm_dispatch(p, 1, MODE_PLAIN, 0, tile_cfg, dtype, (hipStream_t)stream);
 }
 
@@ -210,7 +194,6 @@ int vidi_gemm_qkv_vt_ln(const void* X, const void* Wf, const float* stats, const
     GemmParams p = base_params(X, Wf, nullptr, Yqk, nullptr, M, N, K, ldx, ldw, ldy, 0, 0);
     p.vstart = vstart; p.hd = hd; p.seq = seq; p.seqpad = seqpad; p.nheads = nheads; p.Vt = (u16*)Vt;
     p.ln_stats = stats; p.ln_s = colsum; p.ln_c = shift;
-    if (tile_cfg == 3) return VIDI_ERR_ARG;
     return vidi_gemm_dispatch(p, 1, MODE_QKV_VT, 0, tile_cfg, dtype, (hipStream_t)stream);
 }
 
@@ -222,7 +205,6 @@ int vidi_gemm_kv_cache(const void* X, const void* W, void* Kc, void* Vtc, void* 
     if (kvd % hd || hd % 4 || tok0 < 0 || (tok0 + M + 63) / 64 > ntile64) return VIDI_ERR_SHAPE;
     GemmParams p = base_params(X, W, nullptr, Vrow, nullptr, M, 2 * kvd, K, ldx, ldw, kvd, 0, 0);
     p.Kc = (u16*)Kc; p.Vtc = (u16*)Vtc; p.Vrow = (u16*)Vrow; p.kvd = kvd; p.hd = hd; p.ntile64 = ntile64; p.tok0 = tok0;
-    if (tile_cfg == 3) return VIDI_ERR_ARG;
     return vidi_gemm_dispatch(p, 1, MODE_KV_CACHE, 0, tile_cfg, dtype, (hipStream_t)stream);
 }
 

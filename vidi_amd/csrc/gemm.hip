@@ -11,7 +11,6 @@
 //
 // Roofline: MFMA-bound (2.5 PFLOP/s dense bf16/fp16).  Algorithmic FLOPs = 2*M*N*K.
 #include "kernels.h"
-#include <stdlib.h>
 #include "gemm_w4_launch.h"
 
 // ---- conservative variant: register-staged (global_load -> ds_write), same LDS image ----------
@@ -124,11 +123,6 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
 // =============================================================================================
 // host-side dispatch (C ABI in capi.hip calls these)
 // =============================================================================================
-template <typename K>
-static hipError_t set_lds(K kern, int bytes) {
-    return hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
-
 template <typename T, int BN, int BM, int WN, int WM, int STAGES, int MODE, bool REPKV, int SCHED, int MI>
 static int launch_cfg(const GemmParams& p, int batch, hipStream_t st) {
     constexpr int RING = STAGES * (BN + BM) * 64 * 2;
@@ -136,92 +130,58 @@ static int launch_cfg(const GemmParams& p, int batch, hipStream_t st) {
     constexpr int LDS = RING > CTILE ? RING : CTILE;
     auto kern = gemm_kernel<T, BN, BM, WN, WM, STAGES, MODE, REPKV, SCHED, MI, LabNone>;
     static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = set_lds(kern, LDS);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
+    const hipError_t e = w4_set_lds_once(kern, LDS, attr_done);
+    if (e != hipSuccess) return (int)e;
     const int tiles = ((p.N + BN - 1) / BN) * ((p.M + BM - 1) / BM);
     hipLaunchKernelGGL(kern, dim3(tiles, batch), dim3(WN * WM * 64), LDS, st, p);
     return (int)hipGetLastError();
 }
 
-// persistent 4-wave kernel (gemm_w4.h); VIDI_W4_UNSUPPORTED when this epilogue combination is not instantiated
+// the router's tile-kernel enumerators -> this file's instantiations (gemm_route.h: VIDI_TILE_KERNELS, GK_REGSTAGE)
 template <typename T, int MODE, bool REPKV>
-static int launch_w4_any(const GemmParams& p, int batch, hipStream_t st) {
-    if (p.K % 64 || p.K < 192 || (REPKV && (p.rep_hd % 64))) return VIDI_W4_UNSUPPORTED;      // the K loop needs >= 3 slices
-    if constexpr (MODE == MODE_PLAIN) {
-        if constexpr (T::id == VIDI_DT_BF16) return vidi_w4_plain_bf16(p, batch, REPKV ? 1 : 0, st);
-        else return vidi_w4_plain_f16(p, batch, REPKV ? 1 : 0, st);
-    } else {
-        return vidi_w4_modes(p, batch, MODE, T::id, st);
+static int launch_tile(GemmKernel k, const GemmParams& p, int batch, hipStream_t st) {
+    switch (k) {
+        case GK_REGSTAGE:
+            if constexpr (MODE == MODE_PLAIN) {
+                const int tiles = ((p.N + 127) / 128) * ((p.M + 127) / 128);
+                hipLaunchKernelGGL((gemm_kernel_regstage<T, MODE, REPKV>), dim3(tiles, batch), dim3(256), 0, st, p);
+                return (int)hipGetLastError();
+            }
+            break;
+#define VIDI_TILE_LAUNCH_CASE(name, cfg, BN, BM, WN, WM, STAGES, SCHED, MI, PLAIN_ONLY) \
+        case name: if constexpr (!PLAIN_ONLY || MODE == MODE_PLAIN) return launch_cfg<T, BN, BM, WN, WM, STAGES, MODE, REPKV, SCHED, MI>(p, batch, st); break;
+        VIDI_TILE_KERNELS(VIDI_TILE_LAUNCH_CASE)
+        default: break;
     }
-}
-
-template <typename T, int MODE, bool REPKV>
-static int launch_mode(const GemmParams& p, int batch, int tile_cfg, hipStream_t st) {
-    if (tile_cfg == 3) {
-        if (p.ln_stats) return VIDI_ERR_ARG;
-        if constexpr (MODE == MODE_PLAIN) {
-            const int tiles = ((p.N + 127) / 128) * ((p.M + 127) / 128);
-            hipLaunchKernelGGL((gemm_kernel_regstage<T, MODE, REPKV>), dim3(tiles, batch), dim3(256), 0, st, p);
-            return (int)hipGetLastError();
-        } else {
-            return VIDI_ERR_ARG;
-        }
-    }
-    if (tile_cfg < 0) {
-        // measured on MI355X (tools/lab): the 256x256 tile wins from ~1 wave of blocks up, also when N is not a multiple of
-        // 256 (edge tiles are masked); small problems take the 128x128 tile
-        const long long t256 = (long long)((p.N + 255) / 256) * ((p.M + 255) / 256) * batch;
-        static int big = -1;                      // VIDI_GEMM_CFG: 4 or 5 (A/B of the two large-tile kernels; same results)
-        if (big < 0) { const char* e = getenv("VIDI_GEMM_CFG"); big = e ? atoi(e) : 5; if (big != 4 && big != 5) big = 5; }
-        if (t256 >= 192 && (big == 5 || p.ln_stats)) {            // persistent 4-wave kernel; the 8-wave kernel covers epilogue combinations it lacks
-            const int rc = launch_w4_any<T, MODE, REPKV>(p, batch, st);
-            if (rc != VIDI_W4_UNSUPPORTED) return rc;
-        }
-        tile_cfg = (t256 >= 192 && !p.ln_stats) ? 4 : 0;
-    }
-    if ((p.ln_stats || p.hm_seq) && tile_cfg != 0 && tile_cfg != 5) return VIDI_ERR_ARG;       // folded LayerNorm: persistent kernel or the 128x128 tile
-    switch (tile_cfg) {
-        case 0: return launch_cfg<T, 128, 128, 2, 2, 2, MODE, REPKV, SCHED_RING, 32>(p, batch, st);
-        case 1: return launch_cfg<T, 128, 256, 2, 4, 3, MODE, REPKV, SCHED_RING, 32>(p, batch, st);
-        case 2: return launch_cfg<T, 256, 256, 2, 4, 2, MODE, REPKV, SCHED_RING, 32>(p, batch, st);
-        case 4: return launch_cfg<T, 256, 256, 2, 4, 2, MODE, REPKV, SCHED_LATE, 16>(p, batch, st);    // 8 waves x (128x64), 16x16x32 MFMA
-        case 5: {                                                                                      // persistent, 4 waves x (128x128)
-            const int rc = launch_w4_any<T, MODE, REPKV>(p, batch, st);
-            return rc == VIDI_W4_UNSUPPORTED ? VIDI_ERR_ARG : rc;
-        }
-        case 11:                                                                                        // 192-wide n tile (N = 1152: 6 exact tiles instead of 4.5)
-            if constexpr (MODE == MODE_PLAIN) return launch_cfg<T, 192, 256, 2, 4, 2, MODE, REPKV, SCHED_LATE, 16>(p, batch, st);
-            else return VIDI_ERR_ARG;
-        default: return VIDI_ERR_ARG;
-    }
+    return VIDI_ERR_ARG;
 }
 
 template <typename T>
-static int launch_dtype(const GemmParams& p, int batch, int mode, int repkv, int tile_cfg, hipStream_t st) {
+static int launch_tile_mode(GemmKernel k, const GemmParams& p, int batch, int mode, int repkv, hipStream_t st) {
     switch (mode) {
-        case MODE_PLAIN: return repkv ? launch_mode<T, MODE_PLAIN, true>(p, batch, tile_cfg, st)
-                                      : launch_mode<T, MODE_PLAIN, false>(p, batch, tile_cfg, st);
-        case MODE_GEGLU: return launch_mode<T, MODE_GEGLU, false>(p, batch, tile_cfg, st);
-        case MODE_QKV_VT: return launch_mode<T, MODE_QKV_VT, false>(p, batch, tile_cfg, st);
-        case MODE_KV_CACHE: return launch_mode<T, MODE_KV_CACHE, false>(p, batch, tile_cfg, st);
+        case MODE_PLAIN: return repkv ? launch_tile<T, MODE_PLAIN, true>(k, p, batch, st) : launch_tile<T, MODE_PLAIN, false>(k, p, batch, st);
+        case MODE_GEGLU: return launch_tile<T, MODE_GEGLU, false>(k, p, batch, st);
+        case MODE_QKV_VT: return launch_tile<T, MODE_QKV_VT, false>(k, p, batch, st);
+        case MODE_KV_CACHE: return launch_tile<T, MODE_KV_CACHE, false>(k, p, batch, st);
         default: return VIDI_ERR_ARG;
     }
 }
 
-int vidi_gemm_dispatch(const GemmParams& p, int batch, int mode, int repkv, int tile_cfg, int dtype, hipStream_t st) {
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || batch <= 0) return VIDI_ERR_SHAPE;
-    if (p.K % 64 != 0 || p.N % 32 != 0) return VIDI_ERR_SHAPE;
-    if (mode == MODE_GEGLU && p.N % 64 != 0) return VIDI_ERR_SHAPE;
-    if ((p.ldx % 8) || (p.ldw % 8) || (p.ldy % 8)) return VIDI_ERR_ALIGN;
-    if (((uintptr_t)p.X & 15) || ((uintptr_t)p.W & 15) || ((uintptr_t)p.Y & 15)) return VIDI_ERR_ALIGN;
-    if (p.R && ((p.ldr % 8) || ((uintptr_t)p.R & 15))) return VIDI_ERR_ALIGN;
-    if (mode == MODE_KV_CACHE && (((uintptr_t)p.Kc & 15) || ((uintptr_t)p.Vrow & 15) || (p.hd % 8))) return VIDI_ERR_ALIGN;
-    if (dtype == VIDI_DT_BF16) return launch_dtype<BF16>(p, batch, mode, repkv, tile_cfg, st);
-    if (dtype == VIDI_DT_F16) return launch_dtype<F16>(p, batch, mode, repkv, tile_cfg, st);
-    return VIDI_ERR_DTYPE;
+// validate + route (gemm_route.h), then launch the kernel the route names in the translation unit that instantiates it
+int vidi_gemm_dispatch(const GemmParams& call, int batch, int mode, int repkv, int tile_cfg, int dtype, hipStream_t st) {
+    const GemmRoute r = gemm_route(call, batch, mode, repkv, tile_cfg, dtype, gemm_env());
+    if (r.err) return r.err;
+    GemmParams p = call;
+    if (r.row_partials) p.stat_part = nullptr;           // same partials from one pass over the stored rows, below
+    const bool bf16 = dtype == VIDI_DT_BF16;
+    int rc;
+    if (r.kernel < GK_TILE_END) rc = bf16 ? launch_tile_mode<BF16>(r.kernel, p, batch, mode, repkv, st) : launch_tile_mode<F16>(r.kernel, p, batch, mode, repkv, st);
+    else if (r.kernel < GK_W4_PLAIN_END) rc = bf16 ? vidi_w4_plain_bf16(r.kernel, p, batch, st) : vidi_w4_plain_f16(r.kernel, p, batch, st);
+    else if (r.kernel < GK_W4_LNF_END) rc = vidi_w4_lnf(r.kernel, p, batch, dtype, st);
+    else if (r.kernel < GK_W4_MODES_END) rc = vidi_w4_modes(r.kernel, p, batch, dtype, st);
+    else rc = vidi_w4n(r.kernel, p, dtype, st);
+    if (rc != 0 || !r.row_partials) return rc;
+    return vidi_row_partials_dispatch(p.Y, call.stat_part, p.M, p.N, p.ldy, r.strips, dtype, st);
 }
 
 int vidi_gemm_f32_dispatch(const float* X, const float* W, const float* bias, float* Y, int M, int N, int K,

@@ -758,3 +758,19 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(GemmParams p, int batch) {
         }
     }
 }
+
+// ---- host side, shared by the launchers (launch_cfg in gemm.hip, launch_w4 in gemm_w4_launch.h, launch_w4n in gemm_w4n.h) ----------
+inline int w4_cu_count() {             // the persistent kernels launch one block per CU
+    static const int ncu = [] {
+        int dev = 0, n = 0;
+        const bool ok = hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0;
+        return ok ? n : 256;
+    }();
+    return ncu;
+}
+template <typename K>                  // the kernel's dynamic-LDS limit, raised once per instantiation (`done` is the launcher's own static)
+static hipError_t w4_set_lds_once(K kern, int bytes, bool& done) {
+    const hipError_t e = done ? hipSuccess : hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    done = e == hipSuccess;
+    return e;
+}

@@ -1,3 +1,3 @@
 // persistent 4-wave GEMM, MODE_PLAIN instantiations, bf16 (see gemm_w4_launch.h)
 #include "gemm_w4_launch.h"
-int vidi_w4_plain_bf16(const GemmParams& p, int batch, int repkv, hipStream_t st) { return w4_plain_dispatch<BF16>(p, batch, repkv, st); }
+int vidi_w4_plain_bf16(GemmKernel k, const GemmParams& p, int batch, hipStream_t st) { return w4_plain_launch<BF16>(k, p, batch, st); }

@@ -20,6 +20,7 @@
 // kernel's (same fp32 accumulation order per output element).  Roofline: MFMA-bound; algorithmic FLOPs = 2*M*N*K.
 #pragma once
 #include "gemm_w4.h"
+#include "gemm_route.h"       // w4n_takes(), w4n_stat_strips(): the widths this geometry takes over and its partial-sum layout
 
 struct W4NGeom {
     static constexpr int BN = 288, BM = 224, BK = 64, NT = 256, TN = 9, TM = 7, ROWB = 128;
@@ -31,10 +32,7 @@ struct W4NGeom {
     static_assert(STAGE_BYTES == 65536 && LDS_BYTES <= 163840, "LDS plan");
 };
 
-// partial-sum entries per row that the statistics epilogue of this geometry writes for an output width N
-__host__ __device__ inline int w4n_stat_strips(int N) { return 4 * ((N + W4NGeom::BN - 1) / W4NGeom::BN); }
-// the widths this geometry takes over from the 256-wide kernel
-__host__ __device__ inline bool w4n_takes(int N) { return N >= 288 && N % 288 == 0 && N % 256 != 0; }
+static_assert(W4NGeom::BN == W4N_BN, "gemm_route.h states the n tile");
 
 #ifndef VIDI_W4N_LABTAIL
 #define VIDI_W4N_LABTAIL 0              // lab builds only (wrong results): 1 = the tail's global loads / stores skipped, 2 = no tail work in the epilogue
@@ -463,16 +461,10 @@ template <typename T, typename EPI, typename LAB = LabNone>
 static int launch_w4n(const GemmParams& p, hipStream_t st) {
     auto kern = gemm_w4n_kernel<T, EPI, LAB>;
     static bool attr_done = false;
-    static int ncu = 0;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, W4NGeom::LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-        attr_done = true;
-    }
+    const hipError_t e = w4_set_lds_once(kern, W4NGeom::LDS_BYTES, attr_done);
+    if (e != hipSuccess) return (int)e;
     const long long tiles = (long long)((p.N + W4NGeom::BN - 1) / W4NGeom::BN) * ((p.M + W4NGeom::BM - 1) / W4NGeom::BM);
-    const int grid = (int)(tiles < ncu ? tiles : ncu);
+    const int ncu = w4_cu_count(), grid = (int)(tiles < ncu ? tiles : ncu);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), W4NGeom::LDS_BYTES, st, p);
     return (int)hipGetLastError();
 }
