@@ -809,6 +809,24 @@ class VidiEngine:
         if ts.n_valid is not None:
             ts.n_valid = ts.n_valid.index_select(0, idx)
 
+    def truncate_text_state(self, ts: TextState, n_keep: int) -> None:
+        """Speculative decoding: roll the text cache back to its first `n_keep` slots (the rejected drafts of a verify step).  The stale
+        K/V rows stay where they are: their mask bytes are cleared, and the next step overwrites them before anything reads them."""
+        old = ts.past_len
+        if not 0 <= n_keep <= old:
+            raise ValueError(f"cannot keep {n_keep} of {old} cached text positions")
+        if ts.pos_dev is not None:
+            raise RuntimeError("a graph-captured decode loop owns the cache position: no roll-back")
+        if ts.n_valid is not None:
+            ts.n_valid = ts.n_valid - ts.kmask[:, n_keep: old].sum(-1).to(ts.n_valid.dtype)
+        ts.kmask[:, n_keep: old] = 0
+        ts.past_len = n_keep
+
+    def spec_max_draft(self) -> int:
+        """The most drafts a verify step takes: with k drafts, the k + 1 verify rows times the G query heads of a kv head fill exactly one
+        32-row cross-attention tile (the keys are read once per tile): 15 for Vidi1.5-9B (G = 2), 7 for Vidi-7B (G = 4)."""
+        return 32 // (self.cfg.num_attention_heads // self.cfg.num_key_value_heads) - 1
+
     def _rope_tables(self, max_pos: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """cos/sin rows per position, fp32 math then cast (TP gemma2:118-136); host-precomputed table."""
         if self._rope_cache is None or self._rope_cache[0].shape[0] < max_pos:

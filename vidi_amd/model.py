@@ -20,6 +20,7 @@ from typing import Any, Dict, Optional, Sequence, Tuple
 
 import torch
 
+from . import spec
 from .config import VidiConfig
 from .engine import MMBatchState, MMState, VidiEngine
 
@@ -107,7 +108,7 @@ _UNSUPPORTED_GENERATION_KWARGS = {
     "min_p": None, "typical_p": 1.0, "epsilon_cutoff": 0.0, "eta_cutoff": 0.0, "top_h": None, "num_beam_groups": 1, "diversity_penalty": 0.0,
     "penalty_alpha": None, "dola_layers": None, "encoder_repetition_penalty": 1.0, "begin_suppress_tokens": None, "forced_bos_token_id": None,
     "forced_eos_token_id": None, "exponential_decay_length_penalty": None, "sequence_bias": None, "renormalize_logits": False,
-    "guidance_scale": None, "watermarking_config": None, "prompt_lookup_num_tokens": None, "assistant_model": None, "constraints": None,
+    "guidance_scale": None, "watermarking_config": None, "assistant_model": None, "constraints": None,
     "force_words_ids": None, "prefix_allowed_tokens_fn": None, "remove_invalid_values": False, "token_healing": False, "stop_strings": None,
     "encoder_no_repeat_ngram_size": 0,
 }
@@ -429,7 +430,8 @@ class VidiForCausalLM:
                  audio_sizes: Optional[Sequence[int]] = None, mm_state: Optional[MMState] = None, **kwargs) -> torch.Tensor:
         """gemma.py:603-655.  Accepts do_sample/max_new_tokens/use_cache/disable_compile/pad_token_id/
         attention_mask/position_ids, for do_sample=True: temperature/top_k/top_p/generator (HF warper semantics,
-        vidi_amd/sampling.py), and num_beams/length_penalty/early_stopping/num_return_sequences (HF beam search, vidi_amd/beam.py);
+        vidi_amd/sampling.py), num_beams/length_penalty/early_stopping/num_return_sequences (HF beam search, vidi_amd/beam.py), and
+        prompt_lookup_num_tokens/max_matching_ngram_size (HF prompt-lookup speculative decoding: greedy, one row; vidi_amd/spec.py);
         the reference CLI uses do_sample=False, one beam."""
         if "inputs_embeds" in kwargs:
             raise NotImplementedError("`inputs_embeds` is not supported")            # gemma.py:615-616
@@ -466,6 +468,8 @@ class VidiForCausalLM:
             # `min_length` counts the embedded prompt too (HF's `_prepare_generated_length` under `inputs_embeds`): what is left applies to the new tokens
             n_prompt = int(strip_image_token(inputs, kwargs.get("attention_mask", None))[0].shape[1])
             kwargs["min_length"] = max(int(kwargs["min_length"]) - n_prompt, 0)
+        if kwargs.get("prompt_lookup_num_tokens"):
+            self._check_prompt_lookup(inputs, images, audios, mm_state, kwargs)
         return self._generate_resolved(inputs, images, audios, audio_sizes, mm_state, kwargs)
 
     def _generate_resolved(self, inputs, images, audios, audio_sizes, mm_state, kwargs):
@@ -540,6 +544,8 @@ class VidiForCausalLM:
             # (`_expand_inputs_for_generation`) and draws all rows of a step in one multinomial call — same here, same draws
             ids, mask, pos = (t.repeat_interleave(n_ret, dim=0) for t in (ids, mask, pos))
         ts, last = self._prefill(ids, mask, pos, mm_state, max_new)
+        if kwargs.get("prompt_lookup_num_tokens"):
+            return self._decode_prompt_lookup(ids, mask, ts, last, mm_state, max_new, eos_list, kwargs)
         B = ids.shape[0]
         out = torch.full((B, max_new), int(pad), dtype=torch.int64, device=eng.dev)
         finished = torch.zeros(B, dtype=torch.bool, device=eng.dev)
@@ -637,6 +643,79 @@ class VidiForCausalLM:
             return SimpleNamespace(sequences=out[:, :n_done], scores=None if keep_scores is None else tuple(keep_scores[:n_done]),
                                    logits=None if keep_logits is None else tuple(keep_logits[:n_done]), past_key_values=None)
         return out[:, :n_done]
+
+    # ---- prompt-lookup speculative decoding (HF: generate(prompt_lookup_num_tokens=K, max_matching_ngram_size=N)) ----
+    _spec_draft = staticmethod(spec.lookup_draft)          # test seam: an instance attribute with lookup_draft's signature forces the drafts
+
+    def _check_prompt_lookup(self, inputs, images, audios, mm_state, kwargs) -> None:
+        """what the verify loop does not cover is refused, not ignored"""
+        eng = self.engine
+        K = kwargs["prompt_lookup_num_tokens"]
+        if not isinstance(K, int) or K <= 0 or int(kwargs.get("max_matching_ngram_size", None) or 2) <= 0:
+            raise ValueError("Invalid max_matching_ngram_size or num_output_tokens")                # HF's own check (PromptLookupCandidateGenerator)
+        if inputs.shape[0] != 1 or self._n_videos(images, audios) > 1:
+            raise ValueError("assisted generation is only supported for batch_size = 1")             # HF's own rule
+        if isinstance(mm_state, MMBatchState):
+            raise NotImplementedError("`prompt_lookup_num_tokens` with a batch of different videos is not implemented (one text row, one video)")
+        from .sampling import generation_kwargs_processors
+        procs, crits = generation_kwargs_processors(kwargs, [0], "cpu")
+        blocked = [name for name, on in (("do_sample", bool(kwargs.get("do_sample", False))), ("num_beams", int(kwargs.get("num_beams", None) or 1) > 1),
+                                         ("logits_processor", bool(kwargs.get("logits_processor"))), ("stopping_criteria", bool(kwargs.get("stopping_criteria"))),
+                                         ("a keyword that becomes a logits processor or a stopping criterion (repetition_penalty, max_time, ...)", bool(procs or crits)),
+                                         ("return_dict_in_generate", bool(kwargs.get("return_dict_in_generate")))) if on]
+        if blocked:
+            raise NotImplementedError(f"`prompt_lookup_num_tokens` is greedy, one-beam decoding without per-step hooks: not with {', '.join(blocked)}")
+        if getattr(eng, "sharded", False) or eng.world > 1:
+            raise NotImplementedError("`prompt_lookup_num_tokens` on a sharded engine is not implemented")
+        if not (hasattr(eng, "truncate_text_state") and hasattr(eng, "spec_max_draft")):
+            raise NotImplementedError("`prompt_lookup_num_tokens` needs an engine that can roll its text cache back and states its draft limit "
+                                      "(`truncate_text_state`, `spec_max_draft`)")
+
+    def _decode_prompt_lookup(self, ids, mask, ts, last, mm_state, max_new, eos_list, kwargs):
+        """Greedy decoding of ONE row in which a step may check several drafted tokens at once (vidi_amd/spec.py): the tokens are those of the
+        plain loop wherever the top-2 logit margin exceeds the numeric tolerance (1-row and k-row steps run different projection kernels:
+        the contract of the batched paths); only the number of steps changes.  A request for more drafts than one verify step takes
+        (`engine.spec_max_draft()`: with the last token they fill one 32-row cross-attention tile) is clipped to that.  Steps without a draft are
+        the ordinary Lq = 1 steps; graph-captured decode is off on this path."""
+        eng = self.engine
+        K, N = int(kwargs["prompt_lookup_num_tokens"]), int(kwargs.get("max_matching_ngram_size", None) or 2)
+        assert ids.shape[0] == 1, "one text row"
+        streamer = kwargs.get("streamer")
+        history = [t for t in ids[0][mask[0].bool()].tolist() if t >= 0]      # the prompt's text ids (the <image> placeholder is no token)
+        new = []
+        if streamer is not None:
+            streamer.put(torch.zeros((1, 0), dtype=torch.int64))
+        _, nxt = eng.logits_argmax(last)
+        pending = [int(nxt[0])]                                               # decided tokens not yet handed out; the last one is not in the cache yet
+        done = False
+        while not done:
+            for tok in pending:
+                new.append(tok)
+                history.append(tok)
+                if streamer is not None:
+                    streamer.put(torch.tensor([tok], dtype=torch.int64))
+                if tok in eos_list or len(new) >= max_new:
+                    done = True
+                    break
+            if done:
+                break
+            room = max_new - len(new)
+            k = min(K, eng.spec_max_draft(), room - 1)
+            draft = [int(t) for t in self._spec_draft(history, k, N, eos_list)][:k] if k > 0 else []
+            p0 = ts.past_len
+            step = torch.tensor([new[-1]] + draft, dtype=torch.int64, device=eng.dev)
+            posn = ts.n_valid[0] + torch.arange(len(draft) + 1, dtype=torch.int64, device=eng.dev)      # HF: position = cumsum(mask) - 1 of each new token
+            ts.n_valid += len(draft) + 1
+            hn = eng.text_forward(eng.embed_tokens(step), posn, ts, mm_state, Lq=len(draft) + 1)
+            _, idx = eng.logits_argmax(hn)
+            if not draft:
+                pending = [int(idx[0])]                                         # one D2H sync per step, like the plain loop
+                continue
+            n_accept, pending = spec.accept_run(idx.tolist(), draft, eos_list, room)
+            eng.truncate_text_state(ts, p0 + n_accept + 1)                      # the rejected drafts leave the cache (and `ts.n_valid`)
+        if streamer is not None:
+            streamer.end()
+        return torch.tensor([new], dtype=torch.int64, device=eng.dev)
 
     def _generate_beams(self, ids, mask, pos, mm_state, max_new, num_beams, eos_list, kwargs):
         """`num_beams > 1` (HF `GenerationMixin._beam_search`, reached through gemma.py:646-655's `**kwargs`): vidi_amd/beam.py holds the
