@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define VIDI_ABI_VERSION 6 /* 2: vidi_softcap_argmax takes a caller-owned workspace (the library holds no device state); 3: + vidi_gemm_skinny; 4: (a lab-only revision: LayerNorm statistics in the consumer's K loop, measured 28 % slower, never shipped); 5: + vidi_gemv_mfma (a batch of decode rows on the matrix pipe), vidi_attn_cross_row_tiles_per_block, vidi_probe_*; 6: + vidi_attn_cross_seg, vidi_attn_merge_seg (a batch of different videos decoded together) */
+#define VIDI_ABI_VERSION 6 /* 2: vidi_softcap_argmax takes a caller-owned workspace (the library holds no device state); 3: + vidi_gemm_skinny; 4: (a lab-only revision: LayerNorm statistics in the consumer's K loop, measured 28 % slower, never shipped); 5: + vidi_gemv_mfma (a batch of decode rows on the matrix pipe), vidi_attn_cross_row_tiles_per_block, vidi_probe_*; 6: + vidi_attn_cross_seg, vidi_attn_merge_seg (a batch of different videos decoded together); still 6: + vidi_attn_text_decode_rows (purely additive: one new symbol, no existing signature or layout changes, so the number stays) */
 #define VIDI_DT_BF16 0
 #define VIDI_DT_F16 1
 #define VIDI_DT_F32 2 /* output type of the preprocessing kernels only */
@@ -263,6 +263,18 @@ int vidi_attn_text_dyn(const void* Q, const void* Kc, const void* Vc, const void
 int vidi_attn_text_decode(const void* qkv, int ldqkv, void* Kc, void* Vc, const void* kmask, const void* cos_, const void* sin_, void* O,
                           int B, int Lmax, int nq, int nkv, int HD, int pos0, const int* pos_dev, int window, float scale, float softcap,
                           int dtype, void* stream);
+/* vidi_attn_text_decode for rows AT DIFFERENT LENGTHS (in-flight batching: a finished query frees its cache row and the next one takes
+ * it; same call site, TP gemma2:146-168, 262-275 + gemma.py:165-175 at q_len = 1).  M packed rows: row m owns qkv [m][ldqkv], cos/sin
+ * [m][HD] and O [m][nq*HD]; slots[m] (device int32) is its row of the caches [B][Lmax][nkv*HD] and pos[m] (device int32) the cache
+ * position its token is written to = the number of tokens that row already holds.  Rows are dense (keys 0..pos[m] all valid: no key
+ * mask) and the sliding window counts from pos[m].  pos_max: host-known upper bound of pos[m]; it sizes the LDS score area by
+ * vidi_attn_text_decode's rule at pos0 = pos_max (VIDI_ERR_SHAPE beyond 64 KB).  A record with slots[m] outside [0, B) or pos[m] outside
+ * [0, min(pos_max, Lmax - 1)] is skipped before any access; slots[m] < 0 is the "idle row" value: its output row stays untouched.  Two
+ * rows of one call must not name the same slot.  Per row bit-identical to vidi_attn_text_decode with B = 1 on that slot at pos0 = pos[m].
+ * Added under ABI version 6 without a bump: purely additive. */
+int vidi_attn_text_decode_rows(const void* qkv, int ldqkv, void* Kc, void* Vc, const void* cos_, const void* sin_, void* O, int M,
+                               const int* slots, const int* pos, int pos_max, int B, int Lmax, int nq, int nkv, int HD, int window,
+                               float scale, float softcap, int dtype, void* stream);
 /* vidi_attn_text_decode and vidi_attn_merge2 in ONE launch (the decode step runs the T2V + T2A partial pass first): neither fills the
  * chip and neither depends on the other; the o_proj that follows (gemma.py:94) needs both.  Arguments as in the two calls; results
  * bit-identical to them.  HD 128 or 256. */

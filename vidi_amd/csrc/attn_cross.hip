@@ -61,7 +61,8 @@ __global__ __launch_bounds__(HD) void attn_merge2_kernel(AttnMergeParams a, Attn
 template <typename T, int HD>
 __global__ __launch_bounds__(256) void attn_text_decode_merge2_kernel(AttnTextDecodeParams tp, AttnMergeParams a, AttnMergeParams b, int nt) {
     if ((int)blockIdx.x < nt) {
-        attn_text_decode_body<T, HD>(tp, blockIdx.x % tp.nkv, blockIdx.x / tp.nkv);
+        const int row = blockIdx.x / tp.nkv;
+        attn_text_decode_body<T, HD>(tp, blockIdx.x % tp.nkv, row, row, tp.pos_dev ? *tp.pos_dev : tp.pos0);
         return;
     }
     // the merge role's (m, l) staging lives at the head of the launch's DYNAMIC allocation (sized for the T2T role, never below 2 KB):

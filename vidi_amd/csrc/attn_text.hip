@@ -95,7 +95,9 @@ __global__ __launch_bounds__(64) void attn_text_kernel(AttnTextParams p) {
 }
 
 template <typename T, int HD>
-__global__ __launch_bounds__(256) void attn_text_decode_kernel(AttnTextDecodeParams p) { attn_text_decode_body<T, HD>(p, blockIdx.x, blockIdx.y); }
+__global__ __launch_bounds__(256) void attn_text_decode_kernel(AttnTextDecodeParams p) {
+    attn_text_decode_body<T, HD>(p, blockIdx.x, blockIdx.y, blockIdx.y, p.pos_dev ? *p.pos_dev : p.pos0);
+}
 
 int vidi_attn_text_decode_dispatch(const void* qkv, int ldqkv, void* Kc, void* Vc, const void* kmask, const void* cs, const void* sn,
                                    void* O, int B, int Lmax, int nq, int nkv, int HD, int pos0, const int* pos_dev, int window,

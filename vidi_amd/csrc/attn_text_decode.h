@@ -1,4 +1,5 @@
-// Decode-step T2T body shared by attn_text_decode_kernel (attn_text.hip) and the combined T2T + merge launch (attn_cross.hip).
+// Decode-step T2T body shared by attn_text_decode_kernel (attn_text.hip), the combined T2T + merge launch (attn_cross.hip) and the
+// per-row form over cache slots at different lengths (attn_text_rows.hip).
 #pragma once
 #include "kernels.h"
 
@@ -11,6 +12,8 @@
 //     3. softmax per head by one wave each (P rounded to T, the sum over the unrounded P — attn_text_kernel's and flash-attn's);
 //     4. PV: a thread owns 8 output columns and every (256 / (HD/8))-th key, 8 V rows in flight; the key groups are summed in LDS.
 //   Scores and probabilities are the values attn_text_kernel computes; only the fp32 summation ORDER of the dot products differs.
+//   The body takes the PACKED row `m` (its qkv / cos / sin / output rows), the CACHE row `b` (its K/V rows and key mask) and the position
+//   `pos` as arguments: the batch kernels pass (b, b, the batch's one position), attn_text_rows.hip a table entry per packed row.
 struct AttnTextDecodeParams {
     const u16* qkv; int ldqkv;            // [B][q | k | v] raw projection output of the new token
     u16* Kc; u16* Vc;                     // [B, Lmax, nkv*HD]
@@ -24,7 +27,7 @@ struct AttnTextDecodeParams {
 };
 
 template <typename T, int HD>
-__device__ __forceinline__ void attn_text_decode_body(const AttnTextDecodeParams& p, const int kvh, const int b) {
+__device__ __forceinline__ void attn_text_decode_body(const AttnTextDecodeParams& p, const int kvh, const int m, const int b, const int pos) {
     constexpr int half = HD / 2;
     constexpr int NC = HD / 8;                        // 16-byte chunks per row
     constexpr int CPL = NC / 4;                       // chunks per lane in the score pass (4 lanes per key)
@@ -37,21 +40,20 @@ __device__ __forceinline__ void attn_text_decode_body(const AttnTextDecodeParams
     float* sl = sq + G * HD;                          // [G] softmax denominators (padded to 8)
     float* sc = sl + 8;                               // [G][lcap] scores -> probabilities
     float* red = sc + (size_t)G * p.lcap;             // [NKG][G][HD] PV partials
-    const int pos = p.pos_dev ? *p.pos_dev : p.pos0;
     const int lo = (p.window > 0) ? max(0, pos - p.window) : 0;
     const int n = pos - lo + 1;                       // visible keys lo .. pos
     const size_t kvstride = (size_t)p.nkv * HD;
     u16* kslot = p.Kc + ((size_t)b * p.Lmax + pos) * kvstride + kvh * HD;
     u16* vslot = p.Vc + ((size_t)b * p.Lmax + pos) * kvstride + kvh * HD;
-    const u16* src = p.qkv + (size_t)b * p.ldqkv;
+    const u16* src = p.qkv + (size_t)m * p.ldqkv;
 
     // ---- 1. rope + cache append ----------------------------------------------------------------
     for (int w = tid; w < (G + 1) * half; w += 256) {
         const int hh = w / half, d = w % half;
         const u16* in = (hh < G) ? src + (kvh * G + hh) * HD : src + p.nq * HD + kvh * HD;
         const float x1 = T::to_f32(in[d]), x2 = T::to_f32(in[d + half]);
-        const float c1 = T::to_f32(p.cs[b * HD + d]), c2 = T::to_f32(p.cs[b * HD + d + half]);
-        const float s1 = T::to_f32(p.sn[b * HD + d]), s2 = T::to_f32(p.sn[b * HD + d + half]);
+        const float c1 = T::to_f32(p.cs[m * HD + d]), c2 = T::to_f32(p.cs[m * HD + d + half]);
+        const float s1 = T::to_f32(p.sn[m * HD + d]), s2 = T::to_f32(p.sn[m * HD + d + half]);
         const float y1 = rnd<T>(rnd<T>(x1 * c1) + rnd<T>(-x2 * s1));
         const float y2 = rnd<T>(rnd<T>(x2 * c2) + rnd<T>(x1 * s2));
         if (hh < G) {
@@ -170,7 +172,7 @@ __device__ __forceinline__ void attn_text_decode_body(const AttnTextDecodeParams
         for (int k = 0; k < NKG; ++k) acc += red[((size_t)k * G + g) * HD + d];
         const float lsum = sl[g];
         const float inv = lsum > 0.f ? 1.0f / lsum : 0.f;
-        p.O[(size_t)b * p.nq * HD + (kvh * G + g) * HD + d] = T::from_f32(acc * inv);
+        p.O[(size_t)m * p.nq * HD + (kvh * G + g) * HD + d] = T::from_f32(acc * inv);
     }
 }
 

@@ -405,6 +405,15 @@ int vidi_attn_text_decode(const void* qkv, int ldqkv, void* Kc, void* Vc, const 
                                           softcap, dtype, (hipStream_t)stream);
 }
 
+int vidi_attn_text_decode_rows(const void* qkv, int ldqkv, void* Kc, void* Vc, const void* cos_, const void* sin_, void* O, int M,
+                               const int* slots, const int* pos, int pos_max, int B, int Lmax, int nq, int nkv, int HD, int window,
+                               float scale, float softcap, int dtype, void* stream) {
+    (void)hipGetLastError();
+    if (!qkv || !Kc || !Vc || !cos_ || !sin_ || !O || !slots || !pos) return VIDI_ERR_ARG;
+    return vidi_attn_text_decode_rows_dispatch(qkv, ldqkv, Kc, Vc, cos_, sin_, O, M, slots, pos, pos_max, B, Lmax, nq, nkv, HD, window, scale,
+                                               softcap, dtype, (hipStream_t)stream);
+}
+
 int vidi_attn_text_decode_merge2(const void* qkv, int ldqkv, void* Kc, void* Vc, const void* kmask, const void* cos_, const void* sin_, void* O,
                                  int B, int Lmax, int nq, int nkv, int HD, int pos0, const int* pos_dev, int window, float scale, float softcap,
                                  const float* OpartA, const float* MLA, void* OutA, int WA, int zeroA,

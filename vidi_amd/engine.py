@@ -108,6 +108,18 @@ class TextState:
     pos_idx: Optional[torch.Tensor] = None   # int64 [1] same value, as an index tensor
 
 
+@dataclass
+class TextSlots:
+    """Text KV cache of an in-flight decode loop (vidi_amd/inflight.py): S cache rows ("slots") that sit at DIFFERENT lengths.  A slot is
+    dense — positions 0 .. length[s] - 1 hold one prompt's tokens and nothing else — so there is no key mask; a finished prompt frees its
+    slot (length[s] = -1) and the next waiting prompt takes it.  Consumed by `text_forward(rows=...)` through vidi_attn_text_decode_rows."""
+    S: int
+    Lmax: int
+    kc: torch.Tensor                         # [L, S, Lmax, nkv*hd]
+    vc: torch.Tensor
+    length: List[int]                        # host side: tokens cached per slot; -1 = free
+
+
 class VidiEngine:
     def __init__(self, cfg: VidiConfig, weights: Dict[str, torch.Tensor], dtype: torch.dtype = torch.bfloat16,
                  device: str = "cuda", free_source: bool = True):
@@ -827,6 +839,74 @@ class VidiEngine:
         32-row cross-attention tile (the keys are read once per tile): 15 for Vidi1.5-9B (G = 2), 7 for Vidi-7B (G = 4)."""
         return 32 // (self.cfg.num_attention_heads // self.cfg.num_key_value_heads) - 1
 
+    # ---- in-flight batching: many queries on one resident video, rows at different lengths (DESIGN.md section 14) ----
+    def max_inflight_rows(self) -> int:
+        """The decode rows that fill one 32-row cross-attention tile (`spec_max_draft`'s argument: the video's keys are read once per tile):
+        16 for Vidi1.5-9B (G = 2), 8 for Vidi-7B (G = 4)."""
+        return 32 // (self.cfg.num_attention_heads // self.cfg.num_key_value_heads)
+
+    def new_text_slots(self, S: int, Lmax: int) -> TextSlots:
+        cfg = self.cfg
+        kvd = cfg.num_key_value_heads * cfg.head_dim
+        Lr = cfg.num_hidden_layers
+        with torch.inference_mode(False):
+            return TextSlots(S=S, Lmax=Lmax, kc=torch.zeros((Lr, S, Lmax, kvd), dtype=self.dtype, device=self.dev),
+                             vc=torch.zeros((Lr, S, Lmax, kvd), dtype=self.dtype, device=self.dev), length=[-1] * S)
+
+    def _check_slots(self, tslots: TextSlots, slot_ids, mm, want_free: bool) -> None:
+        if self.sharded or self.world > 1:
+            raise RuntimeError("text slots (in-flight batching) run on one GPU: not on a sharded engine")
+        if isinstance(mm, MMBatchState):
+            raise RuntimeError("text slots (in-flight batching) take ONE resident video, not a batch of different videos")
+        if len(set(slot_ids)) != len(slot_ids) or not slot_ids:
+            raise ValueError(f"slot ids {list(slot_ids)}: one row per slot, at least one")
+        for s_ in slot_ids:
+            if not 0 <= s_ < tslots.S or (tslots.length[s_] < 0) != want_free:
+                raise ValueError(f"slot {s_} of {tslots.S} is {'in use' if want_free else 'free'} (length {tslots.length[s_] if 0 <= s_ < tslots.S else None})")
+
+    def slots_prefill(self, tslots: TextSlots, slot_ids, prompts, mm: Optional[MMState]) -> torch.Tensor:
+        """Admits n prompts (text ids, the <image> placeholder already removed) into n free slots: ONE right-padded ragged prefill (the
+        ordinary `text_forward` path with its varlen packing) into a temporary text state, then each row's first `len` K/V positions of
+        every layer are copied into its slot (data movement, a few MB per prompt: the valid tokens of a right-padded row already sit at
+        cache positions 0 .. len - 1).  Returns the final-norm hidden state of every prompt's last token [n, H]."""
+        slot_ids = [int(s_) for s_ in slot_ids]
+        self._check_slots(tslots, slot_ids, mm, want_free=True)
+        rows = [[int(t) for t in (p.tolist() if torch.is_tensor(p) else p)] for p in prompts]
+        lens = [len(r) for r in rows]
+        n, L = len(rows), max(lens)
+        if n != len(slot_ids) or min(lens) <= 0 or L >= tslots.Lmax:
+            raise ValueError(f"{n} prompts of {lens} tokens for slots {slot_ids} of {tslots.Lmax} positions")
+        ids = torch.full((n, L), -1, dtype=torch.int64)
+        for i, r in enumerate(rows):
+            ids[i, : lens[i]] = torch.tensor(r, dtype=torch.int64)
+        mask = ids >= 0
+        pos = torch.arange(L, dtype=torch.int64).repeat(n, 1) * mask
+        ts = self.new_text_state(n, L)
+        hn = self.text_forward(self.embed_tokens(ids.to(self.dev)), pos.reshape(-1).to(self.dev), ts, mm, Lq=L, new_mask=mask.to(self.dev))
+        for i, (s_, ln) in enumerate(zip(slot_ids, lens)):
+            tslots.kc[:, s_, :ln] = ts.kc[:, i, :ln]
+            tslots.vc[:, s_, :ln] = ts.vc[:, i, :ln]
+            tslots.length[s_] = ln
+        at = torch.tensor([i * L + ln - 1 for i, ln in enumerate(lens)], dtype=torch.int64).to(self.dev)
+        return hn.index_select(0, at)
+
+    def slots_decode(self, tslots: TextSlots, slot_ids, token_ids, mm: Optional[MMState]) -> torch.Tensor:
+        """One decode step for the M listed slots: row m feeds `token_ids[m]` at position length[slot_ids[m]] of its own slot.  The slot,
+        position and token tables come from host integers in ONE small H2D copy.  Returns the final-norm hidden states [M, H]."""
+        slot_ids = [int(s_) for s_ in slot_ids]
+        self._check_slots(tslots, slot_ids, mm, want_free=False)
+        toks = [int(t) for t in (token_ids.tolist() if torch.is_tensor(token_ids) else token_ids)]
+        if len(toks) != len(slot_ids):
+            raise ValueError(f"{len(toks)} tokens for {len(slot_ids)} slots")
+        posl = [tslots.length[s_] for s_ in slot_ids]
+        if max(posl) >= tslots.Lmax:
+            raise RuntimeError("text KV cache exhausted")
+        tab = torch.tensor([slot_ids, posl, toks], dtype=torch.int32).to(self.dev)
+        hn = self.text_forward(self.embed_tokens(tab[2]), tab[1].to(torch.int64), None, mm, Lq=1, rows=(tslots, tab[0], tab[1], max(posl)))
+        for s_ in slot_ids:
+            tslots.length[s_] += 1
+        return hn
+
     def _rope_tables(self, max_pos: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """cos/sin rows per position, fp32 math then cast (TP gemma2:118-136); host-precomputed table."""
         if self._rope_cache is None or self._rope_cache[0].shape[0] < max_pos:
@@ -1033,15 +1113,33 @@ class VidiEngine:
         return all_gather_packed(out, inp, self.pg, async_op=async_op)
 
     def text_forward(self, hidden: torch.Tensor, positions: torch.Tensor, ts: TextState, mm: Optional[MMState],
-                     Lq: int, new_mask: Optional[torch.Tensor] = None, dyn: bool = False) -> torch.Tensor:
+                     Lq: int, new_mask: Optional[torch.Tensor] = None, dyn: bool = False, rows=None) -> torch.Tensor:
         """hidden: [B*Lq, H] embeds already multiplied by the normalizer; positions: int64 [B*Lq].
         Appends Lq positions to the text cache.  Returns the final-norm hidden states [B*Lq, H].
         dyn=True (Lq == 1): the cache slot comes from the device scalars ts.pos_dev / ts.pos_idx, so nothing in the
-        launch sequence depends on the decode position (hipGraph capture); the caller advances them."""
+        launch sequence depends on the decode position (hipGraph capture); the caller advances them.
+        rows=(TextSlots, slots int32 [M], pos int32 [M], pos_max) (Lq == 1, `ts` unused): the M rows of `hidden` are decode rows of M cache
+        slots at different lengths (`slots_decode`); the T2T launch is vidi_attn_text_decode_rows, everything else the row-wise path on M
+        rows.  No key mask or past_len bookkeeping: the caller owns the slots' lengths."""
         cfg = self.cfg
-        B = ts.B
         H, nq, nkv, hd = cfg.hidden_size, cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
         nqd, kvd = nq * hd, nkv * hd
+        if rows is not None:
+            tslots, slots_dev, rpos_dev, pos_max = rows
+            if dyn:
+                raise RuntimeError("rows= (text slots at different lengths) is an eager step: no graph-captured decode (dyn)")
+            if self.sharded:
+                raise RuntimeError("rows= (text slots at different lengths) runs on one GPU: no sharded engine")
+            if isinstance(mm, MMBatchState):
+                raise RuntimeError("rows= (text slots at different lengths) takes one resident video, not an MMBatchState")
+            if Lq != 1 or new_mask is not None:
+                raise RuntimeError("rows= is the single-token decode step (Lq == 1, no new_mask)")
+            for w_ in sorted({cfg.sliding_window if (self.mistral or li % 2 == 0) else 0 for li in range(len(self.layers))}):
+                if not hip.attn_text_decode_rows_fits(nq=nq, nkv=nkv, HD=hd, Lmax=tslots.Lmax, window=w_, pos_max=pos_max):
+                    raise RuntimeError(f"rows=: vidi_attn_text_decode_rows does not fit (head_dim {hd}, {nq // nkv} heads per kv head, window {w_}, "
+                                       f"{pos_max + 1} keys of {tslots.Lmax}): no fallback for text slots")
+            ts = SimpleNamespace(B=int(hidden.shape[0]), Lmax=tslots.Lmax, past_len=0, pos_dev=None, kc=tslots.kc, vc=tslots.vc, kmask=None)
+        B = ts.B
         M = B * Lq
         eps = cfg.rms_norm_eps
         p0 = ts.past_len
@@ -1050,7 +1148,9 @@ class VidiEngine:
         cos_t, sin_t = self._rope_tables(int(ts.Lmax) + 1)
         cos = cos_t.index_select(0, positions).contiguous()
         sin = sin_t.index_select(0, positions).contiguous()
-        if dyn:
+        if rows is not None:
+            pass
+        elif dyn:
             if Lq != 1 or new_mask is not None or ts.pos_dev is None:
                 raise RuntimeError("dyn text_forward is the single-token decode step")
             ts.kmask.index_fill_(1, ts.pos_idx, 1)
@@ -1121,7 +1221,7 @@ class VidiEngine:
             qkv_ready = False
             # RoPE'd q for T2T (raw q stays in qkv for the cross-attention, gemma.py:58), RoPE'd k and v appended to the cache
             window = cfg.sliding_window if (self.mistral or li % 2 == 0) else 0                       # gemma.py:104; Mistral: every layer
-            t2t_fused = Lq == 1 and self.decode_attn and hip.attn_text_decode_fits(nq=nq, nkv=nkv, HD=hd, Lmax=ts.Lmax, window=window,
+            t2t_fused = rows is None and Lq == 1 and self.decode_attn and hip.attn_text_decode_fits(nq=nq, nkv=nkv, HD=hd, Lmax=ts.Lmax, window=window,
                                                                                    pos0=None if dyn else p0)
             t2t_kw = dict(B=B, Lmax=ts.Lmax, nq=nq, nkv=nkv, HD=hd, window=window, scale=sc, softcap=cfg.attn_logit_softcapping, pos0=p0,
                           pos_dev=ts.pos_dev if dyn else None)
@@ -1142,7 +1242,12 @@ class VidiEngine:
                     # collective then runs on RCCL's stream while the T2T launches below execute — same launches, same operands,
                     # same bits as the serial order
                     pending = self._cross_sharded_begin(qkv[:, :nqd], li, mm, outs, R=M * (nq // nkv), async_op=True)
-            if t2t_with_merge:
+            if rows is not None:
+                # in-flight decode rows: rope + append + T2T per row at its own slot and position (never the combined T2T + merge launch)
+                hip.attn_text_decode_rows(qkv, tslots.kc[li], tslots.vc[li], cos, sin, att[:M], slots_dev, rpos_dev, M=M, pos_max=pos_max,
+                                          B=tslots.S, Lmax=tslots.Lmax, nq=nq, nkv=nkv, HD=hd, window=window, scale=sc,
+                                          softcap=cfg.attn_logit_softcapping)
+            elif t2t_with_merge:
                 pass
             elif t2t_fused:
                 # decode: rope + cache append + T2T in one launch (vidi_attn_text_decode)
@@ -1246,7 +1351,7 @@ class VidiEngine:
             else:
                 final_out = torch.empty_like(hidden)
                 hip.resid_norm2(dn, None, None, hidden, L["ln_post_ffn"], self.final_norm, hidden, final_out, eps=eps)
-        if not dyn:
+        if not dyn and rows is None:
             ts.past_len = p0 + Lq
         if prt is not None:
             prt["text_h"].append(hidden.clone())                    # the residual stream after the last layer (before the final norm)

@@ -59,6 +59,7 @@ SIGNATURES = {
     "vidi_attn_text_decode": [_c_vp, _c_int] + [_c_vp] * 6 + [_c_int] * 6 + [_c_vp, _c_int, _c_f, _c_f, _c_int, _c_vp],
     "vidi_attn_text_decode_merge2": [_c_vp, _c_int] + [_c_vp] * 6 + [_c_int] * 6 + [_c_vp, _c_int, _c_f, _c_f] +
                                     ([_c_vp] * 3 + [_c_int] * 2) * 2 + [_c_int] * 4 + [_c_vp],
+    "vidi_attn_text_decode_rows": [_c_vp, _c_int] + [_c_vp] * 5 + [_c_int, _c_vp, _c_vp] + [_c_int] * 7 + [_c_f, _c_f, _c_int, _c_vp],
     "vidi_attn_text": [_c_vp] * 5 + [_c_int] * 8 + [_c_f, _c_f, _c_int, _c_vp],
     "vidi_attn_text_dyn": [_c_vp] * 5 + [_c_int] * 6 + [_c_vp, _c_int, _c_f, _c_f, _c_int, _c_vp],
     "vidi_rope": [_c_vp] * 4 + [_c_int] * 5 + [_c_vp],
@@ -708,6 +709,25 @@ def attn_text_decode(qkv, kc, vc, kmask, cos, sin, out, *, B, Lmax, nq, nkv, HD,
     _check(lib.vidi_attn_text_decode(_p(qkv), qkv.stride(0), _p(kc), _p(vc), _p(kmask), _p(cos), _p(sin), _p(out), B, Lmax, nq, nkv, HD,
                                      int(pos0), _p(pos_dev), int(window), float(scale), float(softcap or 0.0), _dt(qkv), _stream()),
            "vidi_attn_text_decode")
+
+
+def attn_text_decode_rows_fits(*, nq, nkv, HD, Lmax, window, pos_max) -> bool:
+    """whether vidi_attn_text_decode_rows' LDS plan fits its 64 KB: vidi_attn_text_decode's at pos0 = pos_max, the longest row of the step"""
+    return 0 <= pos_max < Lmax and attn_text_decode_fits(nq=nq, nkv=nkv, HD=HD, Lmax=Lmax, window=window, pos0=pos_max)
+
+
+def attn_text_decode_rows(qkv, kc, vc, cos, sin, out, slots, pos, *, M, pos_max, B, Lmax, nq, nkv, HD, window, scale, softcap):
+    """attn_text_decode for M packed rows at different lengths: row m appends to position pos[m] of cache row slots[m] of kc / vc
+    [B, Lmax, nkv*HD] and attends to that row's keys; `slots` / `pos`: int32 device tensors [M] (slots[m] < 0: idle row, skipped)"""
+    lib = load_library()
+    for name, t in (("slots", slots), ("pos", pos)):
+        if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.numel() < M:
+            raise VidiHipError(f"attn_text_decode_rows: {name} must be a contiguous CUDA int32 tensor of at least M = {M} entries")
+    if qkv.shape[0] < M or cos.shape[0] < M or sin.shape[0] < M or out.shape[0] < M or kc.shape[0] < B or vc.shape[0] < B:
+        raise VidiHipError("attn_text_decode_rows: a buffer has fewer rows than the call declares")
+    _check(lib.vidi_attn_text_decode_rows(_p(qkv), qkv.stride(0), _p(kc), _p(vc), _p(cos), _p(sin), _p(out), M, _p(slots), _p(pos), int(pos_max),
+                                          B, Lmax, nq, nkv, HD, int(window), float(scale), float(softcap or 0.0), _dt(qkv), _stream()),
+           "vidi_attn_text_decode_rows")
 
 
 def attn_text_decode_merge2(qkv, kc, vc, kmask, cos, sin, out, merge_a, merge_b, *, B, Lmax, nq, nkv, HD, window, scale, softcap, R, Rpad,

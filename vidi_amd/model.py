@@ -717,6 +717,57 @@ class VidiForCausalLM:
             streamer.end()
         return torch.tensor([new], dtype=torch.int64, device=eng.dev)
 
+    # ---- in-flight batching: many prompts on one resident video (vidi_amd/inflight.py) ----
+    def _check_inflight(self, mm_state, kwargs) -> None:
+        """what the in-flight loop does not cover is refused, not ignored"""
+        from .inflight import SLOT_METHODS
+        from .sampling import generation_kwargs_processors
+        eng = self.engine
+        for k in _UNSUPPORTED_GENERATION_KWARGS:
+            v = kwargs.get(k, None)
+            if v is not None and v is not False and v != _UNSUPPORTED_GENERATION_KWARGS[k]:
+                raise NotImplementedError(f"generate_inflight(): `{k}` is not implemented by the MI355X path")
+        procs, crits = generation_kwargs_processors(kwargs, [0], "cpu")
+        blocked = [name for name, on in (("do_sample", bool(kwargs.get("do_sample", False))), ("num_beams", int(kwargs.get("num_beams", None) or 1) > 1),
+                                         ("logits_processor", bool(kwargs.get("logits_processor"))), ("stopping_criteria", bool(kwargs.get("stopping_criteria"))),
+                                         ("a keyword that becomes a logits processor or a stopping criterion (repetition_penalty, max_time, ...)", bool(procs or crits)),
+                                         ("return_dict_in_generate", bool(kwargs.get("return_dict_in_generate"))),
+                                         ("prompt_lookup_num_tokens", bool(kwargs.get("prompt_lookup_num_tokens")))) if on]
+        blocked += [k for k in ("images", "audios", "streamer", "attention_mask") if kwargs.get(k) is not None]   # (one encoded video; unpadded prompts)
+        if blocked:
+            raise NotImplementedError(f"generate_inflight() is greedy, one-beam decoding without per-step hooks: not with {', '.join(blocked)}")
+        if isinstance(mm_state, MMBatchState):
+            raise NotImplementedError("generate_inflight() takes ONE resident video (`encode_mm_state`), not a batch of different videos")
+        if getattr(eng, "sharded", False) or eng.world > 1:
+            raise NotImplementedError("generate_inflight() on a sharded engine is not implemented")
+        if not all(hasattr(eng, m) for m in SLOT_METHODS):
+            raise NotImplementedError("generate_inflight() needs an engine with text-cache slots (`new_text_slots`, `slots_prefill`, `slots_decode`)")
+
+    @torch.no_grad()
+    def generate_inflight(self, prompts, mm_state: Optional[MMState] = None, max_new_tokens=20, eos_token_id=None, max_rows: Optional[int] = None,
+                          min_admit: int = 2, on_finish=None, **kwargs):
+        """Greedy decoding of MANY prompts against ONE resident video with the decode rows kept full: a prompt that finishes frees its
+        text-cache slot and the next waiting prompt takes it (vidi_amd/inflight.py).  `prompts`: unpadded 1-D id tensors or lists (each may
+        hold the <image> placeholder); `max_new_tokens`: an int or one per prompt; `max_rows`: slots (default `engine.max_inflight_rows()`:
+        one 32-row cross-attention tile; more simply use more tiles); `min_admit`: free slots an admission waits for (2: the measured best of 1 / 2 / 4, profiles/inflight_queries.json); `on_finish(index,
+        tokens)` is called as each prompt completes.  Returns, in input order, each prompt's new tokens (LongTensor, unpadded) up to and
+        including its first EOS, or `max_new_tokens` of them: the tokens of `generate(prompt[None], mm_state=..., max_new_tokens=n)`
+        wherever that run's top-2 logit margin exceeds the numeric tolerance (1-row and M-row steps run different projection kernels: the
+        contract of the batched and speculative paths).  VIDI_DECODE_GRAPH has no effect here."""
+        from .inflight import run_inflight
+        self._check_inflight(mm_state, kwargs)
+        eos = self.generation_config.eos_token_id if eos_token_id is None else eos_token_id
+        eos_list = [int(e) for e in (eos if isinstance(eos, (list, tuple)) else [eos]) if e is not None]
+        texts = []
+        for p in prompts:
+            row = (p if torch.is_tensor(p) else torch.tensor(list(p), dtype=torch.int64)).reshape(1, -1)
+            ids, mask, _ = strip_image_token(row, None)
+            texts.append(ids[0][mask[0]].tolist())
+        n_new = [int(max_new_tokens)] * len(texts) if isinstance(max_new_tokens, int) else [int(m) for m in max_new_tokens]
+        done = None if on_finish is None else (lambda i, toks: on_finish(i, torch.tensor(toks, dtype=torch.int64)))
+        outs = run_inflight(self.engine, texts, mm_state, n_new, eos_list, max_rows=max_rows, min_admit=min_admit, on_finish=done)
+        return [torch.tensor(o, dtype=torch.int64, device=self.engine.dev) for o in outs]
+
     def _generate_beams(self, ids, mask, pos, mm_state, max_new, num_beams, eos_list, kwargs):
         """`num_beams > 1` (HF `GenerationMixin._beam_search`, reached through gemma.py:646-655's `**kwargs`): vidi_amd/beam.py holds the
         search; here: the rows expanded to `num_beams` each before the text prefill, one decode step per search step with the text K/V
