@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define VIDI_ABI_VERSION 6 /* 2: vidi_softcap_argmax takes a caller-owned workspace (the library holds no device state); 3: + vidi_gemm_skinny; 4: (a lab-only revision: LayerNorm statistics in the consumer's K loop, measured 28 % slower, never shipped); 5: + vidi_gemv_mfma (a batch of decode rows on the matrix pipe), vidi_attn_cross_row_tiles_per_block, vidi_probe_*; 6: + vidi_attn_cross_seg, vidi_attn_merge_seg (a batch of different videos decoded together); still 6: + vidi_attn_text_decode_rows (purely additive: one new symbol, no existing signature or layout changes, so the number stays) */
+#define VIDI_ABI_VERSION 6 /* 2: vidi_softcap_argmax takes a caller-owned workspace (the library holds no device state); 3: + vidi_gemm_skinny; 4: (a lab-only revision: LayerNorm statistics in the consumer's K loop, measured 28 % slower, never shipped); 5: + vidi_gemv_mfma (a batch of decode rows on the matrix pipe), vidi_attn_cross_row_tiles_per_block, vidi_probe_*; 6: + vidi_attn_cross_seg, vidi_attn_merge_seg (a batch of different videos decoded together); still 6: + vidi_attn_text_decode_rows (purely additive: one new symbol, no existing signature or layout changes, so the number stays); still 6: + vidi_token_logprob (additive in the same way) */
 #define VIDI_DT_BF16 0
 #define VIDI_DT_F16 1
 #define VIDI_DT_F32 2 /* output type of the preprocessing kernels only */
@@ -349,6 +349,21 @@ int vidi_geglu_unpack(const void* Yp, void* out, int M, int I, int dtype, void* 
  * (the library keeps no device state: SURVEY 8b "stateless, re-entrant ... workspace passed in explicitly"). */
 size_t vidi_softcap_argmax_workspace_bytes(int B);
 int vidi_softcap_argmax(void* logits, long long* idx, int B, int V, long long ld, float cap, int dtype, void* workspace, void* stream);
+/* Per-token log-probabilities (gemma.py:565-590: final softcap, `logits.float()`, cross-entropy — here for one chosen token per row and
+ * without an fp32 [R, V] block).  logits:[R, V] (row stride ld >= V) is the RAW lm_head output and is only read.  With x_i = the softcapped
+ * value T(T(tanh(T(l_i / cap))) * cap) upcast to fp32 (cap > 0; the bits vidi_softcap_argmax stores), or l_i itself (cap <= 0):
+ *   idx[r]      first index of max x (vidi_softcap_argmax's tie rule)
+ *   lse[r]      log sum_i exp(x_i), fp32
+ *   logprob[r]  x_t - lse[r] with t = targets[r];  targets[r] == -1, or targets == NULL for every row: t = idx[r]
+ *   rank[r]     number of i with x_i > x_t, or x_i == x_t and i < t (0 for the greedy token)
+ * A target outside [-1, V) gives logprob = -inf and rank = -1, and nothing is read at that index.  Two launches (per-slice partials, then
+ * one wave per row): no atomics and no zeroed scratch, so a row's outputs are bit-identical from run to run and whatever other rows share
+ * the call.  workspace: R * VIDI_TOKEN_LOGPROB_WORKSPACE_BYTES_PER_ROW bytes, 16-byte aligned, contents irrelevant before and after; its
+ * size is passed in workspace_bytes and checked (null: VIDI_ERR_ARG, misaligned: VIDI_ERR_ALIGN, too small: VIDI_ERR_SHAPE — before any
+ * launch).  Added under ABI version 6 without a bump: purely additive. */
+#define VIDI_TOKEN_LOGPROB_WORKSPACE_BYTES_PER_ROW 2048
+int vidi_token_logprob(const void* logits, const long long* targets, long long* idx, float* lse, float* logprob, int* rank, int R, int V,
+                       long long ld, float cap, int dtype, void* workspace, size_t workspace_bytes, void* stream);
 /* mel:[C,nmel,L] -> [C,L+2,nmel] zero-padded rows for the conv1-as-GEMM view (TP whisper:566,618) */
 int vidi_mel_transpose_pad(const void* mel, void* out, int C, int nmel, int L, int dtype, void* stream);
 /* y = T(x*s): `embeds * normalizer` for externally supplied embeddings (gemma.py:353-356); n % 8 == 0 */

@@ -15,8 +15,8 @@ CSRC = os.path.join(HERE, "csrc")
 _OUT = os.environ.get("VIDI_BUILD_OUT")
 OBJ = os.path.join(_OUT, "obj") if _OUT else os.path.join(CSRC, "build")
 LIB = os.path.join(_OUT, "libvidi_hip.so") if _OUT else os.path.join(HERE, "libvidi_hip.so")
-SOURCES = ["gemm.hip", "gemv.hip", "gemm_w4_bf16.hip", "gemm_w4_f16.hip", "gemm_w4_modes.hip", "gemm_w4_lnf.hip", "gemm_w4_patch.hip", "gemm_w4n.hip", "gemm_skinny.hip", "gemv_mfma.hip", "attn_self.hip", "attn_self_rm.hip", "attn_cross.hip", "attn_cross_seg.hip", "attn_cross_rows.hip", "attn_text.hip", "attn_text_rows.hip", "rowops.hip", "elementwise.hip", "preproc.hip", "probe.hip", "capi.hip"]
-HEADERS = ["common.h", "kernels.h", "gemm_tile.h", "gemm_w4.h", "gemm_w4n.h", "gemm_w4_launch.h", "gemm_route.h", "gemm_skinny.h", "gemm_skinny_api.h", "gemv_mfma_api.h", "attn_text_decode.h", "attn_cross_body.h", os.path.join("..", "..", "include", "vidi_hip.h")]
+SOURCES = ["gemm.hip", "gemv.hip", "gemm_w4_bf16.hip", "gemm_w4_f16.hip", "gemm_w4_modes.hip", "gemm_w4_lnf.hip", "gemm_w4_patch.hip", "gemm_w4n.hip", "gemm_skinny.hip", "gemv_mfma.hip", "attn_self.hip", "attn_self_rm.hip", "attn_cross.hip", "attn_cross_seg.hip", "attn_cross_rows.hip", "attn_text.hip", "attn_text_rows.hip", "rowops.hip", "elementwise.hip", "vocab_logprob.hip", "preproc.hip", "probe.hip", "capi.hip"]
+HEADERS = ["common.h", "kernels.h", "gemm_tile.h", "gemm_w4.h", "gemm_w4n.h", "gemm_w4_launch.h", "gemm_route.h", "gemm_skinny.h", "gemm_skinny_api.h", "gemv_mfma_api.h", "softcap.h", "vocab_logprob_api.h", "attn_text_decode.h", "attn_cross_body.h", os.path.join("..", "..", "include", "vidi_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]      # (+ the resource-usage remark, see _compile)
 # MFMA results in architectural VGPRs: without this hipcc parks the attention accumulators in AGPRs and copies them
 # to VGPRs and back around every softmax step (attn_self: 2192 v_accvgpr moves, 204 registers -> 0 moves, 150)

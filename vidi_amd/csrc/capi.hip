@@ -4,8 +4,10 @@
 #include "attn_text_decode.h"
 #include "gemm_skinny_api.h"
 #include "gemv_mfma_api.h"
+#include "vocab_logprob_api.h"
 #include <stdlib.h>
 #include "../../include/vidi_hip.h"
+static_assert(VIDI_TOKEN_LOGPROB_WORKSPACE_BYTES_PER_ROW == TOKEN_LOGPROB_MAX_PARTS * TOKEN_LOGPROB_PART_BYTES, "workspace macro of vidi_hip.h");
 
 extern "C" {
 
@@ -554,6 +556,17 @@ int vidi_softcap_argmax(void* logits, long long* idx, int B, int V, long long ld
     const long long i[3] = {B, V, ld};
     const float f[1] = {cap};
     return vidi_ew_dispatch(EW_SOFTCAP_ARGMAX, a, i, f, dtype, (hipStream_t)stream);
+}
+
+int vidi_token_logprob(const void* logits, const long long* targets, long long* idx, float* lse, float* logprob, int* rank, int R, int V,
+                       long long ld, float cap, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    (void)hipGetLastError();
+    if (!logits || !idx || !lse || !logprob || !rank || !workspace) return VIDI_ERR_ARG;
+    if (R <= 0 || V <= 0 || ld < V) return VIDI_ERR_SHAPE;
+    if (dtype != VIDI_DT_BF16 && dtype != VIDI_DT_F16) return VIDI_ERR_DTYPE;
+    if (((uintptr_t)workspace & 15) || ((uintptr_t)logits & 1)) return VIDI_ERR_ALIGN;
+    if (workspace_bytes < (size_t)R * VIDI_TOKEN_LOGPROB_WORKSPACE_BYTES_PER_ROW) return VIDI_ERR_SHAPE;
+    return vidi_token_logprob_dispatch(logits, targets, idx, lse, logprob, rank, R, V, ld, cap, dtype, workspace, (hipStream_t)stream);
 }
 
 int vidi_mel_transpose_pad(const void* mel, void* out, int C, int nmel, int L, int dtype, void* stream) {

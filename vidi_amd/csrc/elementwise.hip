@@ -1,6 +1,7 @@
 // Data-movement / elementwise kernels of the Vidi hot path (all HBM-bound, coalesced along the
 // channel axis).  Each kernel cites the reference lines whose arithmetic it reproduces.
 #include "kernels.h"
+#include "softcap.h"
 
 #define GRID_STRIDE(idx, total) \
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < (total); idx += (size_t)gridDim.x * blockDim.x)
@@ -215,10 +216,7 @@ __global__ void geglu_unpack_kernel(const u16* __restrict__ Yp, u16* __restrict_
 //   idx[b] and clears the row's scratch for the next call.  The scratch is CALLER-OWNED (vidi_softcap_argmax_workspace_bytes: 16 bytes per
 //   row = a 64-bit key + a 32-bit arrival counter; zeroed once by the caller, left zeroed by every call): the library holds no state, so
 //   calls on different streams are independent as long as they use different workspaces (stateless, re-entrant).
-struct AmSlot { unsigned long long best; unsigned int count; unsigned int pad; };
-
-template <typename T>
-__device__ __forceinline__ float softcap_value(float x, float cap) { return rnd<T>(rnd<T>(tanhf(rnd<T>(x / cap))) * cap); }
+struct AmSlot { unsigned long long best; unsigned int count; unsigned int pad; };      // (softcap_value<T>: softcap.h, shared with vocab_logprob.hip)
 
 template <typename T>
 __global__ __launch_bounds__(256) void softcap_argmax_kernel(u16* __restrict__ logits, long long* __restrict__ idx, int V,

@@ -1431,6 +1431,38 @@ class VidiEngine:
             ws = self._am_ws = hip.softcap_argmax_workspace(max(256, B), self.dev)
         return ws
 
+    def token_logprobs(self, hn: torch.Tensor, targets: Optional[torch.Tensor] = None, chunk_rows: int = 256):
+        """lm_head + final softcap + log-softmax for ONE token per row (gemma.py:565-590), -> (ids int64 [R], logprob fp32 [R], rank int32
+        [R]): the greedy token of every row, and the log-probability and rank of targets[r] (-1, or no `targets`: the greedy token; the
+        rank counts the vocabulary entries in front of it).  hn: [R, H]; lm_head runs on at most `chunk_rows` rows at a time and
+        vidi_token_logprob reads that chunk's logits in the model dtype: chunk_rows x V x 2 bytes at the peak, never an fp32 [rows, V]."""
+        R = hn.shape[0]
+        chunk_rows = max(1, int(chunk_rows))
+        if targets is not None:
+            targets = targets.reshape(-1).to(device=self.dev, dtype=torch.int64).contiguous()
+            if targets.numel() != R:
+                raise ValueError(f"token_logprobs: {targets.numel()} targets for {R} rows")
+        ws = self.logprob_workspace(min(R, chunk_rows))
+        hn = hn.contiguous()
+        outs = []
+        for r0 in range(0, R, chunk_rows):
+            logits = self.proj(hn[r0: r0 + chunk_rows], self.lm_head)
+            idx, _, lp, rank = hip.token_logprob(logits, None if targets is None else targets[r0: r0 + chunk_rows],
+                                                 self.cfg.final_logit_softcapping, ws)
+            outs.append((idx, lp, rank))
+        if len(outs) == 1:
+            return outs[0]
+        return tuple(torch.cat([o[k] for o in outs]) for k in range(3))
+
+    def logprob_workspace(self, R: int) -> torch.Tensor:
+        """the engine's scratch for vidi_token_logprob (as `argmax_workspace`: one stream at a time, never allocated under graph capture)"""
+        ws = getattr(self, "_lp_ws", None)
+        if ws is None or ws.numel() * 8 < hip.TOKEN_LOGPROB_WORKSPACE_BYTES_PER_ROW * R:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("log-probability workspace must exist before graph capture (run one eager step first)")
+            ws = self._lp_ws = hip.token_logprob_workspace(max(256, R), self.dev)
+        return ws
+
     def embed_tokens(self, ids: torch.Tensor, normalize: bool = True) -> torch.Tensor:
         """embed_tokens(ids) * normalizer (normalize=False: the raw table rows); ids < 0 give zero rows (padding)."""
         ids = ids.reshape(-1).to(torch.int64).contiguous()

@@ -77,6 +77,7 @@ SIGNATURES = {
     "vidi_embed": [_c_vp] * 3 + [_c_int, _c_int, _c_ll, _c_f, _c_int, _c_vp],
     "vidi_geglu_unpack": [_c_vp] * 2 + [_c_int] * 3 + [_c_vp],
     "vidi_softcap_argmax": [_c_vp] * 2 + [_c_int, _c_int, _c_ll, _c_f, _c_int, _c_vp, _c_vp],
+    "vidi_token_logprob": [_c_vp] * 6 + [_c_int, _c_int, _c_ll, _c_f, _c_int, _c_vp, ctypes.c_size_t, _c_vp],
     "vidi_mel_transpose_pad": [_c_vp] * 2 + [_c_int] * 4 + [_c_vp],
     "vidi_sinusoid": [_c_vp] * 2 + [_c_int] * 5 + [_c_vp],
     "vidi_resize_h_u8": [_c_vp] * 4 + [_c_ll, _c_int, _c_int, _c_int, _c_int, _c_vp],
@@ -888,6 +889,43 @@ def softcap_argmax(logits, idx, cap, workspace: Optional[torch.Tensor] = None):
     _check(load_library().vidi_softcap_argmax(_p(logits), _p(idx), B, V, logits.stride(0), float(cap or 0.0), _dt(logits), _p(workspace),
                                               _stream()), "vidi_softcap_argmax")
     return idx
+
+
+TOKEN_LOGPROB_WORKSPACE_BYTES_PER_ROW = 2048      # VIDI_TOKEN_LOGPROB_WORKSPACE_BYTES_PER_ROW (include/vidi_hip.h)
+
+
+def token_logprob_workspace(R: int, device) -> torch.Tensor:
+    """caller-owned scratch of vidi_token_logprob for up to R rows (contents irrelevant before and after a call)"""
+    return torch.empty((int(R) * TOKEN_LOGPROB_WORKSPACE_BYTES_PER_ROW // 8,), dtype=torch.int64, device=device)
+
+
+_lp_ws = {}
+
+
+def token_logprob(logits, targets: Optional[torch.Tensor] = None, cap=None, workspace: Optional[torch.Tensor] = None):
+    """-> (idx int64 [R], lse fp32 [R], logprob fp32 [R], rank int32 [R]) of the RAW logits [R, V], which are only read: first arg-max of the
+    softcapped row, its log-sum-exp, and the log-probability and rank of targets[r] (int64; -1, or no `targets`: the arg-max).  workspace:
+    from token_logprob_workspace (one per stream that may run concurrently); without one, a scratch cached per (device, stream) is used —
+    allocated eagerly on first use, so pass an explicit workspace to calls that are graph-captured."""
+    _rowmajor(logits, "logits")
+    R, V = logits.shape
+    if targets is not None and (targets.dtype != torch.int64 or not targets.is_cuda or not targets.is_contiguous() or targets.numel() != R):
+        raise VidiHipError(f"vidi_token_logprob: targets must be a contiguous CUDA int64 tensor of R = {R} entries")
+    need = R * TOKEN_LOGPROB_WORKSPACE_BYTES_PER_ROW
+    if workspace is None:
+        key = (logits.device.index, _stream())
+        workspace = _lp_ws.get(key)
+        if workspace is None or workspace.numel() * 8 < need:
+            if torch.cuda.is_current_stream_capturing():
+                raise VidiHipError("vidi_token_logprob: pass a pre-allocated workspace when capturing a graph")
+            workspace = _lp_ws[key] = token_logprob_workspace(max(R, 64), logits.device)
+    idx = torch.empty((R,), dtype=torch.int64, device=logits.device)
+    out = torch.empty((2, R), dtype=torch.float32, device=logits.device)
+    rank = torch.empty((R,), dtype=torch.int32, device=logits.device)
+    _check(load_library().vidi_token_logprob(_p(logits), _p(targets), _p(idx), _p(out[0]), _p(out[1]), _p(rank), R, V, logits.stride(0),
+                                             float(cap or 0.0), _dt(logits), _p(workspace), workspace.numel() * workspace.element_size(),
+                                             _stream()), "vidi_token_logprob")
+    return idx, out[0], out[1], rank
 
 
 def mel_transpose_pad(mel, out):

@@ -11,6 +11,7 @@ Host logic only, engine-agnostic (no torch import): the engine supplies
     slots_prefill(slots, slot_ids, prompts, mm) -> last hidden [n, H]     admits n prompts (lists of text ids) into n free slots
     slots_decode(slots, slot_ids, token_ids, mm) -> hidden [M, H]         one step for the M listed slots
     logits_argmax(hidden) -> (logits, ids)
+    token_logprobs(hidden) -> (ids, logprob, rank)                        only with `logprobs=True`: the greedy token's log-probability
 `vidi_amd.engine.VidiEngine` implements them with HIP kernels; tests/test_inflight.py drives this loop with a scripted fake and with the CPU
 oracle."""
 from __future__ import annotations
@@ -25,9 +26,18 @@ def _ids(idx) -> List[int]:
     return [int(t) for t in (idx.tolist() if hasattr(idx, "tolist") else idx)]
 
 
+def _ids_logprobs(ids, lp):
+    """the ids and their log-probabilities on the host.  Device tensors come over in ONE copy: fp64 holds an id and an fp32 value exactly"""
+    if hasattr(ids, "double") and hasattr(lp, "double"):
+        import torch
+        both = torch.stack((ids.double(), lp.double())).tolist()
+        return [int(t) for t in both[0]], both[1]
+    return _ids(ids), [float(x) for x in (lp.tolist() if hasattr(lp, "tolist") else lp)]
+
+
 def run_inflight(engine, prompts: Sequence[Sequence[int]], mm, max_new: Sequence[int], eos_ids: Sequence[int] = (),
                  max_rows: Optional[int] = None, min_admit: int = 2,
-                 on_finish: Optional[Callable[[int, List[int]], None]] = None) -> List[List[int]]:
+                 on_finish: Optional[Callable[[int, List[int]], None]] = None, logprobs: bool = False):
     """prompts[i]: text ids (no placeholder); max_new[i] >= 1.  Returns, in input order, every prompt's new tokens up to and including its
     first EOS, or max_new[i] of them.
 
@@ -36,12 +46,16 @@ def run_inflight(engine, prompts: Sequence[Sequence[int]], mm, max_new: Sequence
     that is complete after it (EOS, max_new == 1) gives its slot back without ever occupying a decode row — the rule is then applied
     again, so with min_admit = 1 no slot idles while a prompt waits (the default is 2: on the measured workload, profiles/inflight_queries.json,
     pairing admissions halves the prefill calls and wins 1.7 % over 1; 4 loses); (2) one `slots_decode` over the live rows, `logits_argmax`, one D2H
-    copy of the ids; (3) finished rows free their slot."""
+    copy of the ids; (3) finished rows free their slot.
+
+    `logprobs=True`: both places that call `logits_argmax` call `engine.token_logprobs(hidden)` instead (the same argmax over the same logits,
+    plus the chosen token's log-probability; ids and values still come over in one D2H copy per step) and the result is (tokens, logprobs):
+    logprobs[i][j] is the log-probability of tokens[i][j], the EOS token's included."""
     n = len(prompts)
     if len(max_new) != n or any(int(m) < 1 for m in max_new):
         raise ValueError("max_new: one count >= 1 per prompt")
     if n == 0:
-        return []
+        return ([], []) if logprobs else []
     S = int(max_rows if max_rows is not None else engine.max_inflight_rows())
     if S < 1 or int(min_admit) < 1:
         raise ValueError(f"max_rows = {S}, min_admit = {min_admit}: both at least 1")
@@ -52,9 +66,20 @@ def run_inflight(engine, prompts: Sequence[Sequence[int]], mm, max_new: Sequence
     live = {}                                              # slot -> prompt index
     last = {}                                              # slot -> the token decided last (not in the cache yet)
     out: List[List[int]] = [[] for _ in range(n)]
+    lps: List[List[float]] = [[] for _ in range(n)]
 
-    def emit(i: int, tok: int) -> bool:
+    def decide(hid):
+        """-> the greedy token of every row (and, with `logprobs`, its log-probability)"""
+        if not logprobs:
+            toks = _ids(engine.logits_argmax(hid)[1])
+            return toks, [None] * len(toks)
+        ids, lp = engine.token_logprobs(hid)[:2]
+        return _ids_logprobs(ids, lp)
+
+    def emit(i: int, tok: int, lp=None) -> bool:
         out[i].append(tok)
+        if lp is not None:
+            lps[i].append(lp)
         done = tok in eos or len(out[i]) >= int(max_new[i])
         if done and on_finish is not None:
             on_finish(i, list(out[i]))
@@ -73,9 +98,9 @@ def run_inflight(engine, prompts: Sequence[Sequence[int]], mm, max_new: Sequence
             sl = [free.pop(0) for _ in range(k)]
             idx = [waiting.popleft() for _ in range(k)]
             hid = engine.slots_prefill(slots, sl, [list(prompts[i]) for i in idx], mm)
-            for s, i, tok in zip(sl, idx, _ids(engine.logits_argmax(hid)[1])):
+            for s, i, tok, lp in zip(sl, idx, *decide(hid)):
                 live[s] = i
-                if emit(i, tok):
+                if emit(i, tok, lp):
                     release(s)
                 else:
                     last[s] = tok
@@ -83,12 +108,12 @@ def run_inflight(engine, prompts: Sequence[Sequence[int]], mm, max_new: Sequence
             continue
         sl = sorted(live)
         hid = engine.slots_decode(slots, sl, [last[s] for s in sl], mm)
-        for s, tok in zip(sl, _ids(engine.logits_argmax(hid)[1])):          # one D2H copy of the ids per step, like the plain loop
-            if emit(live[s], tok):
+        for s, tok, lp in zip(sl, *decide(hid)):                            # one D2H copy per step, like the plain loop
+            if emit(live[s], tok, lp):
                 release(s)
             else:
                 last[s] = tok
-    return out
+    return (out, lps) if logprobs else out
 
 
 def simulate_steps(lengths: Sequence[int], max_rows: int, min_admit: int = 2):

@@ -16,7 +16,7 @@ import os
 
 from dataclasses import dataclass
 from types import SimpleNamespace
-from typing import Any, Dict, Optional, Sequence, Tuple
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -101,6 +101,16 @@ def causal_lm_loss(logits: torch.Tensor, labels: torch.Tensor, loss_thres: Optio
         thres = 0.0 if bool(torch.all(per < loss_thres)) else loss_thres
         return torch.mean(per[per > thres]), flat
     return F.cross_entropy(flat, shift, ignore_index=IGNORE_INDEX, reduction="mean"), flat
+
+
+@dataclass
+class CandidateScore:
+    """one candidate of `VidiForCausalLM.score()`: per-token log-probabilities (fp32 [Lc]) and ranks (int32 [Lc]) on the engine's device,
+    their sum and their mean as Python floats"""
+    token_logprobs: torch.Tensor
+    ranks: torch.Tensor
+    logprob: float
+    mean_logprob: float
 
 
 # HF `GenerationConfig` fields with their neutral values: arguments that alter the decoding and have no counterpart here
@@ -745,7 +755,7 @@ class VidiForCausalLM:
 
     @torch.no_grad()
     def generate_inflight(self, prompts, mm_state: Optional[MMState] = None, max_new_tokens=20, eos_token_id=None, max_rows: Optional[int] = None,
-                          min_admit: int = 2, on_finish=None, **kwargs):
+                          min_admit: int = 2, on_finish=None, output_logprobs: bool = False, **kwargs):
         """Greedy decoding of MANY prompts against ONE resident video with the decode rows kept full: a prompt that finishes frees its
         text-cache slot and the next waiting prompt takes it (vidi_amd/inflight.py).  `prompts`: unpadded 1-D id tensors or lists (each may
         hold the <image> placeholder); `max_new_tokens`: an int or one per prompt; `max_rows`: slots (default `engine.max_inflight_rows()`:
@@ -753,9 +763,14 @@ class VidiForCausalLM:
         tokens)` is called as each prompt completes.  Returns, in input order, each prompt's new tokens (LongTensor, unpadded) up to and
         including its first EOS, or `max_new_tokens` of them: the tokens of `generate(prompt[None], mm_state=..., max_new_tokens=n)`
         wherever that run's top-2 logit margin exceeds the numeric tolerance (1-row and M-row steps run different projection kernels: the
-        contract of the batched and speculative paths).  VIDI_DECODE_GRAPH has no effect here."""
+        contract of the batched and speculative paths).  VIDI_DECODE_GRAPH has no effect here.
+        `output_logprobs=True`: -> (tokens, logprobs); logprobs[i] (fp32, on the engine's device) holds the log-probability of every token
+        of tokens[i], the EOS token's included — `engine.token_logprobs` takes the place of `logits_argmax` (the same argmax over the same
+        logits, so the tokens are the tokens of the call without the flag)."""
         from .inflight import run_inflight
         self._check_inflight(mm_state, kwargs)
+        if output_logprobs and not hasattr(self.engine, "token_logprobs"):
+            raise NotImplementedError("generate_inflight(output_logprobs=True) needs an engine with `token_logprobs`")
         eos = self.generation_config.eos_token_id if eos_token_id is None else eos_token_id
         eos_list = [int(e) for e in (eos if isinstance(eos, (list, tuple)) else [eos]) if e is not None]
         texts = []
@@ -765,8 +780,89 @@ class VidiForCausalLM:
             texts.append(ids[0][mask[0]].tolist())
         n_new = [int(max_new_tokens)] * len(texts) if isinstance(max_new_tokens, int) else [int(m) for m in max_new_tokens]
         done = None if on_finish is None else (lambda i, toks: on_finish(i, torch.tensor(toks, dtype=torch.int64)))
-        outs = run_inflight(self.engine, texts, mm_state, n_new, eos_list, max_rows=max_rows, min_admit=min_admit, on_finish=done)
-        return [torch.tensor(o, dtype=torch.int64, device=self.engine.dev) for o in outs]
+        if not output_logprobs:
+            outs = run_inflight(self.engine, texts, mm_state, n_new, eos_list, max_rows=max_rows, min_admit=min_admit, on_finish=done)
+            return [torch.tensor(o, dtype=torch.int64, device=self.engine.dev) for o in outs]
+        outs, lps = run_inflight(self.engine, texts, mm_state, n_new, eos_list, max_rows=max_rows, min_admit=min_admit, on_finish=done, logprobs=True)
+        return ([torch.tensor(o, dtype=torch.int64, device=self.engine.dev) for o in outs],
+                [torch.tensor(v, dtype=torch.float32, device=self.engine.dev) for v in lps])
+
+    # ---- scoring: the log-probability of given answers behind one prompt ----
+    @torch.no_grad()
+    def score(self, prompt, candidates, mm_state: Optional[MMState] = None, images=None, audios=None, audio_sizes=None,
+              max_positions: int = 512) -> List[CandidateScore]:
+        """Log-probability of each candidate answer as the continuation of `prompt` on one video (multiple-choice evaluation, re-ranking,
+        a confidence next to a retrieved time range).  `prompt`: a 1-D id tensor or list, may hold the <image> placeholder (stripped as in
+        `generate_inflight`); `candidates`: non-empty id lists / tensors.  -> one `CandidateScore` per candidate, in order.
+
+        With P the prompt's length after stripping, token_logprobs[j] is the log-softmax, at position P - 1 + j of the row
+        [prompt | candidate] (the position in front of candidate token j), of the final-softcapped logits rounded to the model dtype and
+        upcast to fp32 — the number `forward(labels=...)`'s cross-entropy is built from (gemma.py:565-590) — taken at candidate token j;
+        ranks[j] counts the vocabulary entries ranked in front of that token (0: it is the greedy token).
+
+        The rows [prompt | candidate_i], right-padded, go through the ragged text prefill, as many per call as keep rows x length <=
+        `max_positions` (always at least one); lm_head runs on the candidate positions only, through `engine.token_logprobs` (no fp32
+        [rows, V] block exists).  An engine without that method (the CPU test engine) gets the same numbers from `logits_argmax`'s logits
+        with torch in fp32.  Every call prefills the prompt again with each candidate: prefilling it once and scoring the candidates as
+        continuations of a shared text cache is the obvious next saving, and not part of this method."""
+        eng = self.engine
+        if isinstance(mm_state, MMBatchState):
+            raise NotImplementedError("score() takes ONE resident video (`encode_mm_state`), not a batch of different videos")
+        if getattr(eng, "sharded", False) or eng.world > 1:
+            raise NotImplementedError("score() on a sharded engine is not implemented")
+        row = (prompt if torch.is_tensor(prompt) else torch.tensor(list(prompt), dtype=torch.int64)).reshape(1, -1)
+        ids, mask, _ = strip_image_token(row, None)
+        text = ids[0][mask[0]].tolist()
+        cands = [[int(t) for t in (c.reshape(-1).tolist() if torch.is_tensor(c) else c)] for c in candidates]
+        if not text or any(len(c) == 0 for c in cands):
+            raise ValueError("score(): the prompt and every candidate hold at least one token")
+        if mm_state is None and (images is not None or audios is not None):
+            mm_state = self.encode_mm_state(images, audios, audio_sizes)
+        P = len(text)
+        groups, cur = [], []
+        for i, c in enumerate(cands):                                     # in order; a group grows while rows x padded length fits
+            if cur and (len(cur) + 1) * (P + max(len(cands[k]) for k in cur + [i])) > int(max_positions):
+                groups.append(cur)
+                cur = []
+            cur.append(i)
+        if cur:
+            groups.append(cur)
+        lp_all, rank_all = [], []
+        for g in groups:
+            B, L = len(g), P + max(len(cands[i]) for i in g)
+            ids = torch.full((B, L), -1, dtype=torch.int64)
+            mask = torch.zeros((B, L), dtype=torch.bool)
+            pos = torch.zeros((B, L), dtype=torch.int64)
+            take = []
+            for b, i in enumerate(g):
+                n = P + len(cands[i])
+                ids[b, :n] = torch.tensor(text + cands[i], dtype=torch.int64)
+                mask[b, :n] = True
+                pos[b, :n] = torch.arange(n)
+                take += [b * L + P - 1 + j for j in range(len(cands[i]))]
+            ts = eng.new_text_state(B, L + 1)
+            hn = eng.text_forward(eng.embed_tokens(ids.to(eng.dev)), pos.reshape(-1).to(eng.dev), ts, mm_state, Lq=L, new_mask=mask.to(eng.dev))
+            hid = hn.view(B * L, -1)[torch.tensor(take, dtype=torch.int64, device=eng.dev)]
+            tgt = torch.tensor([t for i in g for t in cands[i]], dtype=torch.int64, device=eng.dev)
+            if hasattr(eng, "token_logprobs"):
+                _, lp, rank = eng.token_logprobs(hid, tgt)
+            else:                                                         # an engine without the kernel (never VidiEngine): torch, fp32
+                x = eng.logits_argmax(hid.contiguous())[0].float()
+                xt = x.gather(1, tgt[:, None])
+                lp = (xt - torch.logsumexp(x, dim=-1, keepdim=True))[:, 0]
+                col = torch.arange(x.shape[1], device=x.device)[None]
+                rank = ((x > xt) | ((x == xt) & (col < tgt[:, None]))).sum(-1).to(torch.int32)
+            lp_all.append(lp)
+            rank_all.append(rank)
+        lp_all, rank_all = torch.cat(lp_all), torch.cat(rank_all)
+        host = lp_all.double().cpu()                                     # one copy: the sums are formed on the host in fp64
+        out, at = [], 0
+        for c in cands:
+            n = len(c)
+            tot = float(host[at: at + n].sum())
+            out.append(CandidateScore(token_logprobs=lp_all[at: at + n], ranks=rank_all[at: at + n], logprob=tot, mean_logprob=tot / n))
+            at += n
+        return out
 
     def _generate_beams(self, ids, mask, pos, mm_state, max_new, num_beams, eos_list, kwargs):
         """`num_beams > 1` (HF `GenerationMixin._beam_search`, reached through gemma.py:646-655's `**kwargs`): vidi_amd/beam.py holds the
