@@ -124,6 +124,31 @@ _UNSUPPORTED_GENERATION_KWARGS = {
 }
 
 
+def _eos_ids(eos) -> List[int]:
+    """`eos_token_id` as a list: HF allows a list ([1, 107] for Gemma2), one id or None"""
+    return [int(e) for e in (eos if isinstance(eos, (list, tuple)) else [eos]) if e is not None]
+
+
+def _text_ids(prompt) -> List[int]:
+    """one unpadded prompt (a 1-D id tensor or a list, may hold the <image> placeholder) -> its text ids"""
+    row = (prompt if torch.is_tensor(prompt) else torch.tensor(list(prompt), dtype=torch.int64)).reshape(1, -1)
+    ids, mask, _ = strip_image_token(row, None)
+    return ids[0][mask[0]].tolist()
+
+
+# HF generation hooks (GenerationMixin semantics).  The reference drives HF's loop with `inputs_embeds` (gemma.py:646-655), so the
+# `input_ids` these callables see hold the NEW tokens only ([B, 0] at the first step):
+#   logits_processor  [callable(input_ids, scores) -> scores]   applied to the fp32 scores before the argmax / the sampling warpers
+#   stopping_criteria [callable(input_ids, scores) -> bool | BoolTensor[B]]   rows it flags finish like rows that emitted EOS
+# plain keyword arguments HF turns into processors / criteria itself (repetition_penalty, no_repeat_ngram_size, bad_words_ids,
+# min_length, min_new_tokens, suppress_tokens, max_time) come first, in HF's order; the caller's own lists follow
+def _hooks(kwargs, eos_list, dev) -> Tuple[list, list]:
+    """-> (processors, criteria) of one generate() call"""
+    from .sampling import generation_kwargs_processors
+    kw_procs, kw_crits = generation_kwargs_processors(kwargs, eos_list, dev)
+    return kw_procs + list(kwargs.get("logits_processor") or []), kw_crits + list(kwargs.get("stopping_criteria") or [])
+
+
 class _Inner:
     """what `model.get_model()` returns in the reference (DattnGemma2MMModel)"""
 
@@ -214,6 +239,16 @@ class VidiForCausalLM:
         if images is None:
             return None
         return int(sum(int(images[i].shape[0]) for i in range(self._n_videos(images, None))))
+
+    def _row_encoder(self, images, audios, audio_sizes):
+        """-> encode(i): the state of video i of a batch answered row by row.  Both towers run ONCE, now, over the concatenated frames /
+        windows of the batch, and the batch's total frame count sets the token budget (multimodal.py:157-180); from there on the videos
+        are independent, and each one's state is encoded when its row is due."""
+        vis, aud = self._tower_batch(images, audios)
+        budget = self._batch_frames(images)
+        return lambda i: self.encode_mm_state(self._row(images, i), self._row(audios, i), None if audio_sizes is None else [audio_sizes[i]],
+                                              vis_features=None if vis is None else vis[i], aud_features=None if aud is None else aud[i],
+                                              budget_frames=budget)
 
     def _shard_on(self) -> bool:
         """True once `engine.set_dist()` made this process one rank of a frame-sharded group (either dist mode)"""
@@ -407,7 +442,6 @@ class VidiForCausalLM:
             at += q.shape[0]
         if not as_dict:
             return out
-        from types import SimpleNamespace
         if hasattr(rows[0], "sequences_scores"):                                  # beam search
             sc = [r.sequences_scores for r in rows]
             return SimpleNamespace(sequences=out, sequences_scores=None if sc[0] is None else torch.cat(sc))
@@ -435,6 +469,57 @@ class VidiForCausalLM:
         last = hn.view(B, L, -1)[torch.arange(B, device=eng.dev), lens - 1]
         return ts, last
 
+    def _step(self, ts, tokens: torch.Tensor, mm_state) -> torch.Tensor:
+        """The one place that turns new tokens into a `text_forward` call: `tokens` holds Lq ids per row of `ts`, row-major (Lq = 1: an
+        ordinary decode step; more: the verify step of prompt-lookup decoding).  Token j of a row sits at position n_valid + j (HF: position =
+        cumsum(mask) - 1 of each new token), and `ts.n_valid` advances by Lq; what shortens or regathers the cache afterwards
+        (`truncate_text_state`, `reorder_text_state`) is the engine's and adjusts `n_valid` itself.  -> the hidden states [B * Lq, H].
+        (`engine.decode_step_dyn` is the graph-captured twin of the Lq = 1 case.)"""
+        eng = self.engine
+        Lq = tokens.numel() // ts.B
+        emb = eng.embed_tokens(tokens)
+        if Lq == 1:
+            posn = ts.n_valid.clone()
+        else:
+            posn = (ts.n_valid[:, None] + torch.arange(Lq, dtype=torch.int64, device=eng.dev)).reshape(-1)
+        ts.n_valid += Lq
+        return eng.text_forward(emb, posn, ts, mm_state, Lq=Lq)
+
+    def _warp(self, logits: torch.Tensor, kwargs, min_tokens_to_keep: int = 1) -> torch.Tensor:
+        """HF's sampling warpers with the caller's knobs, `generation_config`'s where the caller names none (an explicit None switches a
+        warper off)"""
+        from .sampling import warp_logits
+        knob = lambda k: kwargs[k] if k in kwargs else getattr(self.generation_config, k, None)     # noqa: E731
+        return warp_logits(logits, knob("temperature"), knob("top_k"), knob("top_p"), min_tokens_to_keep)
+
+    def _refuse(self, name: str, kwargs, mm_state=None, hint: Optional[str] = None, per_step=None, one_video: bool = True) -> None:
+        """What an entry point does not cover is refused, not ignored.  `name`: the entry point as its messages call it; the checks, in
+        their order:
+          `hint` (a text, may be empty): `kwargs` are a caller's — an HF generation argument that WOULD change the output and has no
+            counterpart here (`_UNSUPPORTED_GENERATION_KWARGS`) is refused, with `hint` closing the message;
+          `per_step` (a list of further (what, given) pairs): the entry point is greedy, one-beam decoding without per-step hooks;
+          `one_video`: it takes one resident video (no `MMBatchState`) on one GPU (no sharded engine)."""
+        eng = self.engine
+        if hint is not None:
+            for k in _UNSUPPORTED_GENERATION_KWARGS:
+                v = kwargs.get(k, None)
+                if v is not None and v is not False and v != _UNSUPPORTED_GENERATION_KWARGS[k]:
+                    raise NotImplementedError(f"{name}: `{k}` is not implemented by the MI355X path{hint}")
+        if per_step is not None:
+            from .sampling import generation_kwargs_processors
+            procs, crits = generation_kwargs_processors(kwargs, [0], "cpu")
+            hooks = [("do_sample", bool(kwargs.get("do_sample", False))), ("num_beams", int(kwargs.get("num_beams", None) or 1) > 1),
+                     ("logits_processor", bool(kwargs.get("logits_processor"))), ("stopping_criteria", bool(kwargs.get("stopping_criteria"))),
+                     ("a keyword that becomes a logits processor or a stopping criterion (repetition_penalty, max_time, ...)", bool(procs or crits)),
+                     ("return_dict_in_generate", bool(kwargs.get("return_dict_in_generate")))]
+            blocked = [what for what, given in hooks + list(per_step) if given]
+            if blocked:
+                raise NotImplementedError(f"{name} is greedy, one-beam decoding without per-step hooks: not with {', '.join(blocked)}")
+        if one_video and isinstance(mm_state, MMBatchState):
+            raise NotImplementedError(f"{name} takes ONE resident video (`encode_mm_state`), not a batch of different videos")
+        if one_video and (getattr(eng, "sharded", False) or eng.world > 1):
+            raise NotImplementedError(f"{name} on a sharded engine is not implemented")
+
     @torch.no_grad()
     def generate(self, inputs: Optional[torch.Tensor] = None, images=None, image_sizes=None, audios=None,
                  audio_sizes: Optional[Sequence[int]] = None, mm_state: Optional[MMState] = None, **kwargs) -> torch.Tensor:
@@ -447,11 +532,8 @@ class VidiForCausalLM:
             raise NotImplementedError("`inputs_embeds` is not supported")            # gemma.py:615-616
         # HF generation arguments that WOULD change the output and that this loop does not implement: refuse them instead of ignoring them
         # (anything a caller needs from this list can be handed over as a ready `logits_processor` / `stopping_criteria` object)
-        for k in _UNSUPPORTED_GENERATION_KWARGS:
-            v = kwargs.get(k, None)
-            if v is not None and v is not False and v != _UNSUPPORTED_GENERATION_KWARGS[k]:
-                raise NotImplementedError(f"generate(): `{k}` is not implemented by the MI355X path (pass an equivalent `logits_processor` / "
-                                          "`stopping_criteria` object, or use the arguments listed in INTEGRATION.md section 5)")
+        self._refuse("generate()", kwargs, hint=" (pass an equivalent `logits_processor` / `stopping_criteria` object, or use the arguments "
+                     "listed in INTEGRATION.md section 5)", one_video=False)
         do_sample = bool(kwargs.get("do_sample", False))
         num_beams = int(kwargs.get("num_beams", None) or 1)
         n_ret = int(kwargs.get("num_return_sequences", None) or 1)
@@ -464,11 +546,12 @@ class VidiForCausalLM:
         # `_generate_resolved` recurse into it (not into this function) with the resolved values, so nothing is subtracted twice and no caller-visible
         # keyword can switch the resolution off
         max_new = kwargs.get("max_new_tokens", None)
+        if max_new is None or kwargs.get("min_length"):
+            n_prompt = int(strip_image_token(inputs, kwargs.get("attention_mask", None))[0].shape[1])      # the batch's embedded prompt positions
         if max_new is None:
             # HF's `_prepare_generated_length` under `inputs_embeds` (how the reference drives it, gemma.py:646-655): `max_length` (default
             # 20) counts the batch's embedded prompt positions only when the caller set it; `max_new_tokens` wins when both are given
             max_length = kwargs.get("max_length", None)
-            n_prompt = int(strip_image_token(inputs, kwargs.get("attention_mask", None))[0].shape[1])
             max_new = 20 if max_length is None else int(max_length) - n_prompt
             if max_new <= 0:
                 raise ValueError(f"Input length of input_ids is {n_prompt}, but `max_length` is set to {max_length}. This can lead to "
@@ -476,7 +559,6 @@ class VidiForCausalLM:
         kwargs = dict(kwargs, max_new_tokens=int(max_new))
         if kwargs.get("min_length"):
             # `min_length` counts the embedded prompt too (HF's `_prepare_generated_length` under `inputs_embeds`): what is left applies to the new tokens
-            n_prompt = int(strip_image_token(inputs, kwargs.get("attention_mask", None))[0].shape[1])
             kwargs["min_length"] = max(int(kwargs["min_length"]) - n_prompt, 0)
         if kwargs.get("prompt_lookup_num_tokens"):
             self._check_prompt_lookup(inputs, images, audios, mm_state, kwargs)
@@ -484,13 +566,10 @@ class VidiForCausalLM:
 
     def _generate_resolved(self, inputs, images, audios, audio_sizes, mm_state, kwargs):
         """generate() behind its argument checks, with `max_new_tokens` / `min_length` already counted in NEW tokens (resolved once per call)"""
-        do_sample = bool(kwargs.get("do_sample", False))
         num_beams = int(kwargs.get("num_beams", None) or 1)
         n_ret = int(kwargs.get("num_return_sequences", None) or 1)
         max_new = int(kwargs["max_new_tokens"])
-        kwargs = dict(kwargs)
-        eos = kwargs.get("eos_token_id", self.generation_config.eos_token_id)
-        eos_list = [int(e) for e in (eos if isinstance(eos, (list, tuple)) else [eos]) if e is not None]     # HF allows a list ([1, 107] for Gemma2)
+        eos_list = _eos_ids(kwargs.get("eos_token_id", self.generation_config.eos_token_id))
         pad = kwargs.get("pad_token_id", None)
         pad = (eos_list[0] if eos_list else 0) if pad is None else pad
         if num_beams > 1:
@@ -517,35 +596,14 @@ class VidiForCausalLM:
         if mm_state is None and self._n_videos(images, audios) > 1:
             # one video PER ROW (multimodal.py:156-252 batches them with pad_sequence + masks): rows never interact, so each
             # row is answered against its own video, unpadded, and the answers are re-padded — the same tokens
-            B = self._n_videos(images, audios)
-            assert inputs.shape[0] == B, "one prompt per video"
-            # both towers ONCE over the concatenated frames / windows of the batch, and the batch's total frame count for the token
-            # budget (multimodal.py:157-180); from there on the videos are independent
-            vis, aud = self._tower_batch(images, audios)
-            budget = self._batch_frames(images)
-            rows = []
-            for i in range(B):
-                kw = dict(kwargs)
-                kw["attention_mask"] = None
-                am_i = None if attention_mask is None else attention_mask[i].bool().cpu()
-                ids_i = inputs[i].cpu() if am_i is None else inputs[i].cpu()[am_i]
-                mm_i = self.encode_mm_state(self._row(images, i), self._row(audios, i), None if audio_sizes is None else [audio_sizes[i]],
-                                            vis_features=None if vis is None else vis[i], aud_features=None if aud is None else aud[i],
-                                            budget_frames=budget)
-                rows.append(self._generate_resolved(ids_i[None], None, None, None, mm_i, kw))
-                del mm_i
-            return self._stack_rows(rows, pad, kwargs)
+            assert inputs.shape[0] == self._n_videos(images, audios), "one prompt per video"
+            return self._generate_row_by_row(inputs, attention_mask, self._row_encoder(images, audios, audio_sizes), pad, kwargs)
         if mm_state is None and (images is not None or audios is not None):
             mm_state = self.encode_mm_state(images, audios, audio_sizes)
         if attention_mask is not None and inputs.shape[0] > 1 and not bool(attention_mask[:, 0].bool().all()):
             # LEFT-padded batch (what Vidi-7B demands for batched generation, mistral.py:366-373; multimodal.py:413-421 re-pads
             # on the tokenizer's side): rows never interact, so every row is decoded unpadded against the shared video state
-            rows = []
-            for i in range(inputs.shape[0]):
-                kw = dict(kwargs)
-                kw["attention_mask"] = None
-                rows.append(self._generate_resolved(inputs[i].cpu()[attention_mask[i].bool().cpu()][None], None, None, None, mm_state, kw))
-            return self._stack_rows(rows, pad, kwargs)
+            return self._generate_row_by_row(inputs, attention_mask, lambda i: mm_state, pad, kwargs)
         ids, mask, pos = strip_image_token(inputs, attention_mask)
         if num_beams > 1:
             return self._generate_beams(ids, mask, pos, mm_state, max_new, num_beams, eos_list, kwargs)
@@ -556,21 +614,30 @@ class VidiForCausalLM:
         ts, last = self._prefill(ids, mask, pos, mm_state, max_new)
         if kwargs.get("prompt_lookup_num_tokens"):
             return self._decode_prompt_lookup(ids, mask, ts, last, mm_state, max_new, eos_list, kwargs)
-        B = ids.shape[0]
+        return self._decode_rows(ts, last, mm_state, max_new, pad, eos_list, kwargs)
+
+    def _generate_row_by_row(self, inputs, attention_mask, mm_of_row, pad, kwargs):
+        """Rows never interact: every row of a padded batch is decoded on its own, stripped to its attended ids, and the answers are
+        re-padded (`_stack_rows`) — the same tokens.  `mm_of_row(i)`: the video state row i is answered against."""
+        kw = dict(kwargs, attention_mask=None)
+        rows = []
+        for i in range(inputs.shape[0]):
+            ids_i = inputs[i].cpu()
+            if attention_mask is not None:
+                ids_i = ids_i[attention_mask[i].bool().cpu()]
+            rows.append(self._generate_resolved(ids_i[None], None, None, None, mm_of_row(i), kw))
+        return self._stack_rows(rows, pad, kwargs)
+
+    def _decode_rows(self, ts, last, mm_state, max_new, pad, eos_list, kwargs):
+        """the greedy / sampling loop over the rows of a prefilled text state (`last`: the hidden state of each row's last prompt token);
+        a streamer gets .put(LongTensor[B]) per step and .end() after the last one"""
+        eng = self.engine
+        B = ts.B
+        do_sample = bool(kwargs.get("do_sample", False))
         out = torch.full((B, max_new), int(pad), dtype=torch.int64, device=eng.dev)
         finished = torch.zeros(B, dtype=torch.bool, device=eng.dev)
         eos_t = torch.tensor(eos_list, dtype=torch.int64, device=eng.dev)
-        # HF generation hooks (GenerationMixin semantics).  The reference drives HF's loop with `inputs_embeds` (gemma.py:646-655), so the
-        # `input_ids` these callables see hold the NEW tokens only ([B, 0] at the first step):
-        #   logits_processor  [callable(input_ids, scores) -> scores]   applied to the fp32 scores before the argmax / the sampling warpers
-        #   stopping_criteria [callable(input_ids, scores) -> bool | BoolTensor[B]]   rows it flags finish like rows that emitted EOS
-        #   streamer          .put(LongTensor[B]) per step, .end() after the last one
-        # plain keyword arguments HF turns into processors / criteria itself (repetition_penalty, no_repeat_ngram_size, bad_words_ids,
-        # min_length, min_new_tokens, suppress_tokens, max_time) come first, in HF's order; the caller's own lists follow
-        from .sampling import generation_kwargs_processors
-        kw_procs, kw_crits = generation_kwargs_processors(kwargs, eos_list, eng.dev)
-        processors = kw_procs + list(kwargs.get("logits_processor") or [])
-        criteria = kw_crits + list(kwargs.get("stopping_criteria") or [])
+        processors, criteria = _hooks(kwargs, eos_list, eng.dev)
         streamer = kwargs.get("streamer")
 
         # `return_dict_in_generate=True`: HF's GenerateDecoderOnlyOutput fields that have a meaning here — `.sequences`, and per step
@@ -589,10 +656,8 @@ class VidiForCausalLM:
                     logits = proc(out[:, :step], logits)
                 idx = torch.argmax(logits, dim=-1)
             if do_sample:
-                from .sampling import sample, warp_logits
-                gc = self.generation_config
-                knob = lambda k: kwargs[k] if k in kwargs else getattr(gc, k, None)     # noqa: E731  an explicit None switches a warper off
-                logits = warp_logits(logits, knob("temperature"), knob("top_k"), knob("top_p"))
+                from .sampling import sample
+                logits = self._warp(logits, kwargs)
                 idx = sample(logits, kwargs.get("generator"))
             if keep_scores is not None:
                 keep_scores.append(logits.float().clone())
@@ -638,17 +703,12 @@ class VidiForCausalLM:
                 else:
                     nxt = replay(nxt).clone()
                 continue
-            emb = eng.embed_tokens(nxt)
-            posn = ts.n_valid.clone()                                  # HF: position = cumsum(mask) - 1 of the new token
-            ts.n_valid += 1
-            hn = eng.text_forward(emb, posn, ts, mm_state, Lq=1)
-            nxt, scores = pick(hn, step + 1)
+            nxt, scores = pick(self._step(ts, nxt, mm_state), step + 1)
             if sync_pick:
                 nxt = self._bcast0(nxt)
         if streamer is not None:
             streamer.end()
         if as_dict:
-            from types import SimpleNamespace
             # (a step's scores exist only if the loop went on to that step: n_done entries, like HF's tuples)
             return SimpleNamespace(sequences=out[:, :n_done], scores=None if keep_scores is None else tuple(keep_scores[:n_done]),
                                    logits=None if keep_logits is None else tuple(keep_logits[:n_done]), past_key_values=None)
@@ -665,18 +725,9 @@ class VidiForCausalLM:
             raise ValueError("Invalid max_matching_ngram_size or num_output_tokens")                # HF's own check (PromptLookupCandidateGenerator)
         if inputs.shape[0] != 1 or self._n_videos(images, audios) > 1:
             raise ValueError("assisted generation is only supported for batch_size = 1")             # HF's own rule
-        if isinstance(mm_state, MMBatchState):
+        if isinstance(mm_state, MMBatchState):                                                      # (in its own words, and ahead of the hooks)
             raise NotImplementedError("`prompt_lookup_num_tokens` with a batch of different videos is not implemented (one text row, one video)")
-        from .sampling import generation_kwargs_processors
-        procs, crits = generation_kwargs_processors(kwargs, [0], "cpu")
-        blocked = [name for name, on in (("do_sample", bool(kwargs.get("do_sample", False))), ("num_beams", int(kwargs.get("num_beams", None) or 1) > 1),
-                                         ("logits_processor", bool(kwargs.get("logits_processor"))), ("stopping_criteria", bool(kwargs.get("stopping_criteria"))),
-                                         ("a keyword that becomes a logits processor or a stopping criterion (repetition_penalty, max_time, ...)", bool(procs or crits)),
-                                         ("return_dict_in_generate", bool(kwargs.get("return_dict_in_generate")))) if on]
-        if blocked:
-            raise NotImplementedError(f"`prompt_lookup_num_tokens` is greedy, one-beam decoding without per-step hooks: not with {', '.join(blocked)}")
-        if getattr(eng, "sharded", False) or eng.world > 1:
-            raise NotImplementedError("`prompt_lookup_num_tokens` on a sharded engine is not implemented")
+        self._refuse("`prompt_lookup_num_tokens`", kwargs, mm_state, per_step=[])
         if not (hasattr(eng, "truncate_text_state") and hasattr(eng, "spec_max_draft")):
             raise NotImplementedError("`prompt_lookup_num_tokens` needs an engine that can roll its text cache back and states its draft limit "
                                       "(`truncate_text_state`, `spec_max_draft`)")
@@ -714,10 +765,7 @@ class VidiForCausalLM:
             draft = [int(t) for t in self._spec_draft(history, k, N, eos_list)][:k] if k > 0 else []
             p0 = ts.past_len
             step = torch.tensor([new[-1]] + draft, dtype=torch.int64, device=eng.dev)
-            posn = ts.n_valid[0] + torch.arange(len(draft) + 1, dtype=torch.int64, device=eng.dev)      # HF: position = cumsum(mask) - 1 of each new token
-            ts.n_valid += len(draft) + 1
-            hn = eng.text_forward(eng.embed_tokens(step), posn, ts, mm_state, Lq=len(draft) + 1)
-            _, idx = eng.logits_argmax(hn)
+            _, idx = eng.logits_argmax(self._step(ts, step, mm_state))
             if not draft:
                 pending = [int(idx[0])]                                         # one D2H sync per step, like the plain loop
                 continue
@@ -728,31 +776,6 @@ class VidiForCausalLM:
         return torch.tensor([new], dtype=torch.int64, device=eng.dev)
 
     # ---- in-flight batching: many prompts on one resident video (vidi_amd/inflight.py) ----
-    def _check_inflight(self, mm_state, kwargs) -> None:
-        """what the in-flight loop does not cover is refused, not ignored"""
-        from .inflight import SLOT_METHODS
-        from .sampling import generation_kwargs_processors
-        eng = self.engine
-        for k in _UNSUPPORTED_GENERATION_KWARGS:
-            v = kwargs.get(k, None)
-            if v is not None and v is not False and v != _UNSUPPORTED_GENERATION_KWARGS[k]:
-                raise NotImplementedError(f"generate_inflight(): `{k}` is not implemented by the MI355X path")
-        procs, crits = generation_kwargs_processors(kwargs, [0], "cpu")
-        blocked = [name for name, on in (("do_sample", bool(kwargs.get("do_sample", False))), ("num_beams", int(kwargs.get("num_beams", None) or 1) > 1),
-                                         ("logits_processor", bool(kwargs.get("logits_processor"))), ("stopping_criteria", bool(kwargs.get("stopping_criteria"))),
-                                         ("a keyword that becomes a logits processor or a stopping criterion (repetition_penalty, max_time, ...)", bool(procs or crits)),
-                                         ("return_dict_in_generate", bool(kwargs.get("return_dict_in_generate"))),
-                                         ("prompt_lookup_num_tokens", bool(kwargs.get("prompt_lookup_num_tokens")))) if on]
-        blocked += [k for k in ("images", "audios", "streamer", "attention_mask") if kwargs.get(k) is not None]   # (one encoded video; unpadded prompts)
-        if blocked:
-            raise NotImplementedError(f"generate_inflight() is greedy, one-beam decoding without per-step hooks: not with {', '.join(blocked)}")
-        if isinstance(mm_state, MMBatchState):
-            raise NotImplementedError("generate_inflight() takes ONE resident video (`encode_mm_state`), not a batch of different videos")
-        if getattr(eng, "sharded", False) or eng.world > 1:
-            raise NotImplementedError("generate_inflight() on a sharded engine is not implemented")
-        if not all(hasattr(eng, m) for m in SLOT_METHODS):
-            raise NotImplementedError("generate_inflight() needs an engine with text-cache slots (`new_text_slots`, `slots_prefill`, `slots_decode`)")
-
     @torch.no_grad()
     def generate_inflight(self, prompts, mm_state: Optional[MMState] = None, max_new_tokens=20, eos_token_id=None, max_rows: Optional[int] = None,
                           min_admit: int = 2, on_finish=None, output_logprobs: bool = False, **kwargs):
@@ -767,17 +790,17 @@ class VidiForCausalLM:
         `output_logprobs=True`: -> (tokens, logprobs); logprobs[i] (fp32, on the engine's device) holds the log-probability of every token
         of tokens[i], the EOS token's included — `engine.token_logprobs` takes the place of `logits_argmax` (the same argmax over the same
         logits, so the tokens are the tokens of the call without the flag)."""
-        from .inflight import run_inflight
-        self._check_inflight(mm_state, kwargs)
+        from .inflight import SLOT_METHODS, run_inflight
+        # what the in-flight loop does not cover (one encoded video; unpadded prompts)
+        self._refuse("generate_inflight()", kwargs, mm_state, hint="",
+                     per_step=[("prompt_lookup_num_tokens", bool(kwargs.get("prompt_lookup_num_tokens")))]
+                     + [(k, kwargs.get(k) is not None) for k in ("images", "audios", "streamer", "attention_mask")])
+        if not all(hasattr(self.engine, m) for m in SLOT_METHODS):
+            raise NotImplementedError("generate_inflight() needs an engine with text-cache slots (`new_text_slots`, `slots_prefill`, `slots_decode`)")
         if output_logprobs and not hasattr(self.engine, "token_logprobs"):
             raise NotImplementedError("generate_inflight(output_logprobs=True) needs an engine with `token_logprobs`")
-        eos = self.generation_config.eos_token_id if eos_token_id is None else eos_token_id
-        eos_list = [int(e) for e in (eos if isinstance(eos, (list, tuple)) else [eos]) if e is not None]
-        texts = []
-        for p in prompts:
-            row = (p if torch.is_tensor(p) else torch.tensor(list(p), dtype=torch.int64)).reshape(1, -1)
-            ids, mask, _ = strip_image_token(row, None)
-            texts.append(ids[0][mask[0]].tolist())
+        eos_list = _eos_ids(self.generation_config.eos_token_id if eos_token_id is None else eos_token_id)
+        texts = [_text_ids(p) for p in prompts]
         n_new = [int(max_new_tokens)] * len(texts) if isinstance(max_new_tokens, int) else [int(m) for m in max_new_tokens]
         done = None if on_finish is None else (lambda i, toks: on_finish(i, torch.tensor(toks, dtype=torch.int64)))
         if not output_logprobs:
@@ -806,13 +829,8 @@ class VidiForCausalLM:
         with torch in fp32.  Every call prefills the prompt again with each candidate: prefilling it once and scoring the candidates as
         continuations of a shared text cache is the obvious next saving, and not part of this method."""
         eng = self.engine
-        if isinstance(mm_state, MMBatchState):
-            raise NotImplementedError("score() takes ONE resident video (`encode_mm_state`), not a batch of different videos")
-        if getattr(eng, "sharded", False) or eng.world > 1:
-            raise NotImplementedError("score() on a sharded engine is not implemented")
-        row = (prompt if torch.is_tensor(prompt) else torch.tensor(list(prompt), dtype=torch.int64)).reshape(1, -1)
-        ids, mask, _ = strip_image_token(row, None)
-        text = ids[0][mask[0]].tolist()
+        self._refuse("score()", {}, mm_state)
+        text = _text_ids(prompt)
         cands = [[int(t) for t in (c.reshape(-1).tolist() if torch.is_tensor(c) else c)] for c in candidates]
         if not text or any(len(c) == 0 for c in cands):
             raise ValueError("score(): the prompt and every candidate hold at least one token")
@@ -870,9 +888,7 @@ class VidiForCausalLM:
         rows re-gathered from their parent beams, and HF's output conventions (the new tokens only, as under `inputs_embeds`; unfinished
         positions hold `pad_token_id`, or the first EOS id when that is None / 0 — HF's `pad_token_id or eos_token_id[0]`;
         `return_dict_in_generate=True` -> an object with `.sequences` and, with `output_scores=True`, `.sequences_scores`)."""
-        from types import SimpleNamespace
         from .beam import beam_search
-        from .sampling import generation_kwargs_processors
         eng = self.engine
         B, nb = ids.shape[0], num_beams
         nrs = int(kwargs.get("num_return_sequences", None) or 1)
@@ -880,9 +896,7 @@ class VidiForCausalLM:
             raise ValueError(f"`num_return_sequences` ({nrs}) has to be smaller or equal to `num_beams` ({nb}).")
         rep = lambda t: t.repeat_interleave(nb, dim=0)                          # noqa: E731  rows b*nb .. b*nb + nb - 1 = the beams of prompt b
         ts, last = self._prefill(rep(ids), rep(mask), rep(pos), mm_state, max_new)
-        kw_procs, kw_crits = generation_kwargs_processors(kwargs, eos_list, eng.dev)
-        processors = kw_procs + list(kwargs.get("logits_processor") or [])
-        criteria = kw_crits + list(kwargs.get("stopping_criteria") or [])
+        processors, criteria = _hooks(kwargs, eos_list, eng.dev)
         if eng.world > 1 and criteria:
             # the greedy loop broadcasts rank 0's stop decisions; beam search evaluates its criteria inside vidi_amd/beam.py on every rank, and a
             # wall-clock (`max_time`) or caller-supplied criterion may differ between ranks: one rank would leave the per-layer all-gathers early
@@ -890,11 +904,8 @@ class VidiForCausalLM:
         do_sample = bool(kwargs.get("do_sample", False))
         if do_sample:
             # beam-search multinomial sampling: HF appends the warpers to the processors (they see the log-probabilities)
-            from .sampling import warp_logits
-            gc = self.generation_config
-            knob = lambda k: kwargs[k] if k in kwargs else getattr(gc, k, None)     # noqa: E731
             keep = max(2, len(eos_list) + 1)                               # HF: top-k / top-p keep at least n_eos + 1 tokens under beams
-            processors = processors + [lambda input_ids, scores: warp_logits(scores, knob("temperature"), knob("top_k"), knob("top_p"), keep)]
+            processors = processors + [lambda input_ids, scores: self._warp(scores, kwargs, keep)]
             if eng.world > 1:
                 raise NotImplementedError("beam-search sampling over a sharded video (every rank would draw its own continuations)")
         fill = kwargs.get("pad_token_id", None) or (eos_list[0] if eos_list else -1)
@@ -903,10 +914,7 @@ class VidiForCausalLM:
         def step_logits(tokens, parents):
             if parents is not None:
                 eng.reorder_text_state(ts, parents)
-            emb = eng.embed_tokens(tokens)
-            posn = ts.n_valid.clone()
-            ts.n_valid += 1
-            return eng.logits_argmax(eng.text_forward(emb, posn, ts, mm_state, Lq=1))[0]
+            return eng.logits_argmax(self._step(ts, tokens, mm_state))[0]
 
         seqs, scores = beam_search(step_logits, eng.logits_argmax(last)[0], B, nb, int(self.config.vocab_size), max_new, eos_list, int(fill),
                                    processors, criteria, 1.0 if length_penalty is None else float(length_penalty),
@@ -937,15 +945,11 @@ class VidiForCausalLM:
             ids_all, mask_all, _ = strip_image_token(input_ids, attention_mask)
             L = ids_all.shape[1]
             outs, states = [], []
-            vis, aud = self._tower_batch(images, audios)                       # the towers once over the batch; batch-wide token budget
-            budget = self._batch_frames(images)
+            encode_row = self._row_encoder(images, audios, audio_sizes)          # the towers once over the batch; batch-wide token budget
             for i in range(B):
                 am_i = None if attention_mask is None else attention_mask[i].bool().cpu()
                 ids_i = input_ids[i].cpu() if am_i is None else input_ids[i].cpu()[am_i]
-                mm_i = self.encode_mm_state(self._row(images, i), self._row(audios, i), None if audio_sizes is None else [audio_sizes[i]],
-                                            vis_features=None if vis is None else vis[i], aud_features=None if aud is None else aud[i],
-                                            budget_frames=budget)
-                r = self.forward(ids_i[None], mm_state=mm_i, logits_to_keep=0)
+                r = self.forward(ids_i[None], mm_state=encode_row(i), logits_to_keep=0)
                 outs.append(r.logits[0])
                 states.append((r.past_key_values, r.past_image_key_values))
             full = torch.zeros((B, L, outs[0].shape[-1]), dtype=outs[0].dtype, device=eng.dev)
