@@ -371,7 +371,20 @@ def test_ragged_batch_runs_on_the_valid_positions_only(tiny_setup, monkeypatch):
     km = mask[None, :, :, None].expand(ka.shape[0], -1, -1, ka.shape[-1])
     report("varlen vs padded: text K cache rows", ka[:, :, : mask.shape[1]][km], kb[:, :, : mask.shape[1]][km], *tol(dt, 1.0, tight=True))
     report("varlen vs padded: text V cache rows", va[:, :, : mask.shape[1]][km], vb[:, :, : mask.shape[1]][km], *tol(dt, 1.0, tight=True))
-    assert torch.equal(ta[:, :1], tb[:, :1]), (ta.tolist(), tb.tolist())
+    # the same first greedy token wherever the padded arm's top-2 margin decides it beyond the logit bound asserted above (twice the bound:
+    # either arm may move either logit by it); where it does not, each arm's token is within that distance of the other arm's best.  Prompt 4
+    # in fp16 is such a row: tokens 443 and 433 tie exactly in the varlen arm and are one fp16 ulp (0.0005) apart in the padded one, against a
+    # bound of 0.005 — which of the two wins there is decided by one rounding anywhere upstream.  The other 7 rows have margins of 0.05 .. 0.29.
+    rows = torch.arange(len(prompts))
+    last = mask.long().cumsum(1).argmax(1)                                       # each prompt's last valid position
+    a_last, b_last = la[rows, last], lb[rows, last]
+    top2 = b_last.topk(2, dim=1).values
+    slack = 2 * (at + rt * top2[:, 0].abs())
+    decided = (top2[:, 0] - top2[:, 1]) > slack
+    assert int(decided.sum()) >= len(prompts) - 1, decided.tolist()
+    assert torch.equal(ta[decided, 0], tb[decided, 0]), (ta.tolist(), tb.tolist())
+    assert bool((b_last[rows, ta[:, 0]] >= top2[:, 0] - slack).all()) and bool((a_last[rows, tb[:, 0]] >= a_last.max(dim=1).values - slack).all()), \
+        (ta.tolist(), tb.tolist())
 
 
 def test_real_dims_two_layers():

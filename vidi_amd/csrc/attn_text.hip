@@ -133,8 +133,8 @@ __global__ void rope_kernel(u16* Q, u16* K, const u16* cs, const u16* sn, int ro
         const float x1 = T::to_f32(base[d]), x2 = T::to_f32(base[d + half]);
         const float c1 = T::to_f32(cs[row * HD + d]), c2 = T::to_f32(cs[row * HD + d + half]);
         const float s1 = T::to_f32(sn[row * HD + d]), s2 = T::to_f32(sn[row * HD + d + half]);
-        const float y1 = rnd<T>(x1 * c1) + rnd<T>(-x2 * s1);
-        const float y2 = rnd<T>(x2 * c2) + rnd<T>(x1 * s2);
+        float y1, y2;
+        rope_pair<T>(x1, x2, c1, c2, s1, s2, y1, y2);
         base[d] = T::from_f32(y1);
         base[d + half] = T::from_f32(y2);
     }
@@ -167,8 +167,8 @@ __global__ void rope_cache_kernel(const u16* __restrict__ qkv, int ldqkv, u16* _
         const float x1 = T::to_f32(in[d]), x2 = T::to_f32(in[d + half]);
         const float c1 = T::to_f32(cs[row * HD + d]), c2 = T::to_f32(cs[row * HD + d + half]);
         const float s1 = T::to_f32(sn[row * HD + d]), s2 = T::to_f32(sn[row * HD + d + half]);
-        const float y1 = rnd<T>(x1 * c1) + rnd<T>(-x2 * s1);
-        const float y2 = rnd<T>(x2 * c2) + rnd<T>(x1 * s2);
+        float y1, y2;
+        rope_pair<T>(x1, x2, c1, c2, s1, s2, y1, y2);
         u16* out = (hh < nq) ? QR + (row * nq + hh) * HD : Kc + slot + (hh - nq) * HD;
         out[d] = T::from_f32(y1);
         out[d + half] = T::from_f32(y2);

@@ -3,6 +3,17 @@
 #pragma once
 #include "kernels.h"
 
+// RoPE of one (d, d + HD/2) pair, rotate_half form: each product and the sum round to the model dtype as eager torch does (the callers
+// round the sum when they store it).  Contraction is OFF here: the compiler narrows the fp16 form of these lines to half arithmetic
+// (exact: an fp32 product of two halves rounded once IS the half product) and, with contraction allowed, then fuses a product into the
+// sum as one v_fma_f16 — one of the two products no longer rounds, and the result differs from eager torch by an ulp now and then.
+template <typename T>
+__device__ __forceinline__ void rope_pair(float x1, float x2, float c1, float c2, float s1, float s2, float& y1, float& y2) {
+#pragma clang fp contract(off)
+    y1 = rnd<T>(x1 * c1) + rnd<T>(-x2 * s1);
+    y2 = rnd<T>(x2 * c2) + rnd<T>(x1 * s2);
+}
+
 // ---- the decode step's T2T in ONE launch: RoPE of the new token's q and k, the KV-cache append and the attention over the cache ----
 //   (was rope_cache_kernel + attn_text_kernel: 5 + 17 us per layer at ~70 keys, the second a chain of ~18 dependent L2 round trips in
 //   one wave).  One 256-thread block per (kv head, batch row) serves the G query heads that share the head's K/V:
@@ -54,8 +65,10 @@ __device__ __forceinline__ void attn_text_decode_body(const AttnTextDecodeParams
         const float x1 = T::to_f32(in[d]), x2 = T::to_f32(in[d + half]);
         const float c1 = T::to_f32(p.cs[m * HD + d]), c2 = T::to_f32(p.cs[m * HD + d + half]);
         const float s1 = T::to_f32(p.sn[m * HD + d]), s2 = T::to_f32(p.sn[m * HD + d + half]);
-        const float y1 = rnd<T>(rnd<T>(x1 * c1) + rnd<T>(-x2 * s1));
-        const float y2 = rnd<T>(rnd<T>(x2 * c2) + rnd<T>(x1 * s2));
+        float y1, y2;
+        rope_pair<T>(x1, x2, c1, c2, s1, s2, y1, y2);
+        y1 = rnd<T>(y1);
+        y2 = rnd<T>(y2);
         if (hh < G) {
             sq[hh * HD + d] = y1;
             sq[hh * HD + d + half] = y2;
